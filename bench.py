@@ -10,9 +10,13 @@ N > 1 (launched by torch.distributed.run): scan points are sharded across
 ranks (map replicated), with one RCCL all-reduce of the 8 x 91 fp64
 super-chunk sums per iteration (strong scaling: the same 100k scan at every N).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the fused
-search pass, timed with HIP events on its own stream over the timed region)
-and `cpu_baseline` (the CPU oracle port, 3 OpenMP threads = MP_PROC_NUM).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+steps and prints the line; `--full` adds what takes runs of its own: `roofline`
+(dominant kernel = the fused search pass, timed with HIP events on its own
+stream), `roofline_l2`, the kNN certificate counts, the Python caller loop
+beside the native one and `cpu_baseline` (the CPU oracle port, 3 OpenMP
+threads = MP_PROC_NUM).  `--dump-outputs DIR` writes what the last timed step
+returned to its caller (x, P, stats) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -541,7 +545,7 @@ def bench_c5(args, rank, world, dev, dist):
     rp = replay.Replay(mp, frames, device=dev, iters=args.iters, cell=args.cell)
     cell_m = rp.cell()
     rp.verify()
-    single = rp.solo_rate(max(10, args.steps // 4), args.warmup) if rank == 0 else None
+    single = rp.solo_rate(max(10, args.steps // 4), args.warmup) if rank == 0 and args.full else None
 
     def before():
         if world > 1:
@@ -862,7 +866,20 @@ def main():
                     help="collective backend for N > 1 (nccl = RCCL over xGMI; gloo only to "
                          "rehearse the multi-rank path with several ranks on one GPU)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "search_traffic.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the roofline's kernel timing (HIP "
+                         "events on further steps), roofline_l2, the kNN certificate counts, the Python "
+                         "caller loop and the CPU baseline (each still switched off by its own --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2: after the timed steps write what the last of them returned to its caller "
+                         "as DIR/x.npy (the 26 state doubles in slio_state order), DIR/P.npy (24 x 24) and "
+                         "DIR/stats.npy (passes, searches, valid_passes, converged, last_m), float64")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "c2":
+        ap.error("--dump-outputs covers the c2 workload")
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_python_reference = True
 
     rc = resolve_gpus(args)
     if rc is not None:
@@ -1019,16 +1036,21 @@ def main():
     ms = C.c_double()
     nl = C.c_int64()
     lib.slio_profile(h, 0)  # reset totals
-    if not args.no_kernel_timing:
+    events = not args.no_kernel_timing
+    if events or not args.full:
         # (a fresh map index gets its block rows after 8 unchanged search
         # passes, kBlkAfterPasses: those updates stay out of the timing)
         for _ in range(3):
             step()
-        lib.slio_profile(h, search_bit)
+        # a plain run takes the same steps without the events: they bring the
+        # GPU out of idle and the map index to its steady state at any --warmup
+        if events:
+            lib.slio_profile(h, search_bit)
         for k in range(max(1, args.timing_steps)):
             step()
-        lib.slio_profile(h, search_bit | L.SLIO_PROFILE_KEEP)
-        lib.slio_profile_read(h, L.SLIO_KERNEL_SEARCH, C.byref(ms), C.byref(nl))
+        if events:
+            lib.slio_profile(h, search_bit | L.SLIO_PROFILE_KEEP)
+            lib.slio_profile_read(h, L.SLIO_KERNEL_SEARCH, C.byref(ms), C.byref(nl))
     lib.slio_profile(h, 0)
     run(args.warmup)
     if world > 1:
@@ -1040,6 +1062,15 @@ def main():
     if world > 1:
         dist.barrier()
     el = time.perf_counter() - t0
+    # x, P and stats as the last timed step left them with its caller
+    last_x = np.frombuffer(C.string_at(xs_a, xs_n), np.float64).copy()
+    last_P = P.copy()
+    last_stats = np.array([stats.passes, stats.searches, stats.valid_passes, stats.converged, stats.last_m],
+                          np.float64)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("x", last_x), ("P", last_P), ("stats", last_stats)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     # the same steps from the Python loop, for reference (not `value`)
     py_el = None
     if loop is not None and not args.no_python_reference:
@@ -1079,7 +1110,8 @@ def main():
     # 1 .. maxit passes from the same prior (fixed flow: the same first passes),
     # after the timed region: the counters cost two atomics per workgroup
     knn = {"label": "exact 5-NN every iteration (searched or certified)"}
-    if args.mode == "fixed" and not args.host_loop and world == 1 and hasattr(lib, "slio_debug_knn_cert"):
+    if (args.full and args.mode == "fixed" and not args.host_loop and world == 1
+            and hasattr(lib, "slio_debug_knn_cert")):
         cc = (C.c_uint32 * 2)()
         L.check(lib.slio_debug_knn_cert(h, cc), "knn_cert")
         cert, srch = [], []
@@ -1100,7 +1132,7 @@ def main():
     # cannot run inside this process): only for the same workload, one rank
     # holding the whole scan, and the library built from the same sources
     traffic = None
-    if (os.path.exists(args.traffic_json) and world == 1 and shard_pts == args.scan_points
+    if (args.full and os.path.exists(args.traffic_json) and world == 1 and shard_pts == args.scan_points
             and args.mode == "fixed"):
         try:
             tj = json.load(open(args.traffic_json))
@@ -1215,6 +1247,8 @@ def main():
         "cpu_baseline": cpu,
         "result_digest": digest,
     }
+    if not args.full:
+        out["roofline"] = None  # no kernel timing in a plain run
     if rank == 0:
         print(json.dumps(out), flush=True)
     lib.slio_destroy(h)

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 tag=${1:-r06b}
 part=${2:-1}
-B="timeout -k 10 400 python bench.py"
+B="timeout -k 10 400 python bench.py --full"
 if [ $part = 1 ]; then
 bash scripts/pmc_search.sh $tag || exit 2
 bash scripts/pmc_frontend.sh $tag || exit 3

@@ -7,7 +7,7 @@ tag=${1:-r06f}
 timeout -k 10 600 python -u -m pytest tests/test_gpu_frontend.py tests/test_gpu_lego.py -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/${tag}_tests.log 2>&1 || { tail -30 gpurun_out/${tag}_tests.log; exit 3; }
 tail -1 gpurun_out/${tag}_tests.log
 bash scripts/pmc_frontend.sh $tag || exit 4
-B="timeout -k 10 300 python bench.py"
+B="timeout -k 10 300 python bench.py --full"
 $B --workload c3 > gpurun_out/${tag}_bench_c3.json 2>gpurun_out/${tag}_bench_c3.err || exit 5
 $B --workload lego > gpurun_out/${tag}_bench_lego.json 2>gpurun_out/${tag}_bench_lego.err || exit 6
 for w in c3 lego; do

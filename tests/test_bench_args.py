@@ -35,3 +35,9 @@ def test_gpus_more_than_visible():
 def test_gpus_must_be_positive():
     r = _run(["--gpus", "0"])
     assert r.returncode == 2 and "--gpus must be >= 1" in r.stderr, r.stderr[-2000:]
+
+
+def test_dump_outputs_is_for_c2(tmp_path):
+    r = _run(["--workload", "lego", "--dump-outputs", str(tmp_path / "d")])
+    assert r.returncode == 2 and "--dump-outputs covers the c2 workload" in r.stderr, r.stderr[-2000:]
+    assert not (tmp_path / "d").exists()

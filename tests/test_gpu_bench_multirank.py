@@ -49,9 +49,36 @@ def test_bench_gpus_spawns_its_ranks():
 
 def test_bench_reference_flow_line():
     """--mode reference --iters 3 (the drop-in's control flow, mapping_avia.launch:11):
-    a bench line whose passes include reuse passes, with a roofline."""
-    ref = _run([sys.executable, "bench.py", *SMALL, "--mode", "reference", "--iters", "3"])
+    a bench line whose passes include reuse passes, with a roofline (--full:
+    a plain run takes no kernel timing)."""
+    ref = _run([sys.executable, "bench.py", *SMALL, "--full", "--mode", "reference", "--iters", "3"])
     cfg = ref["config"]
     assert cfg["control_flow"] == "reference" and cfg["maximum_iter"] == 3
     assert 1 <= cfg["searches_per_step"] <= cfg["iterations_per_step"] <= 4
     assert ref["value"] > 0 and ref["roofline"]["achieved"] > 0
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run prints the headline line without the --full figures, runs
+    exactly --steps timed steps, and --dump-outputs writes what the last timed
+    step returned (x, P, stats) -- the same bits from run to run."""
+    import numpy as np
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        lines.append(_run([sys.executable, "bench.py", "--gpus", "1", *SMALL[:-1], "--dump-outputs", str(d)]))
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("x", "P", "stats")})
+        assert sorted(os.listdir(d)) == ["P.npy", "stats.npy", "x.npy"]
+    one = lines[0]
+    assert one["steps"] == 5 and one["ms_per_step"] > 0
+    assert abs(one["value"] * one["ms_per_step"] * 1e-3 / one["config"]["iterations_per_step"] - 1) < 1e-9
+    assert one["roofline"] is None and one["roofline_l2"] is None and one["cpu_baseline"] is None
+    assert one["config"]["python_loop_value"] is None
+    a, b = dumps
+    assert a["x"].shape == (26,) and a["P"].shape == (24, 24) and a["stats"].shape == (5,)
+    for n in a:
+        assert a[n].dtype == np.float64 and np.isfinite(a[n]).all()
+        assert np.array_equal(a[n], b[n]), n
+    assert a["stats"][0] == one["config"]["iterations_per_step"]
+    assert a["stats"][4] == one["config"]["effective_points"]
+    assert lines[1]["result_digest"] == one["result_digest"]
