@@ -196,6 +196,13 @@ SIGNATURES = {
     "slio_s2m_get_coeffs": (C.c_int, [_P, _FP, _U8P]),
     "slio_s2m_normal_equations": (C.c_int, [_P, _P, _FP, _FP, _FP, _I64P]),
     "slio_s2m_lm_step": (C.c_int, [_FP, _FP, C.c_int64, C.c_int, _FP, _IP, _FP, _IP]),
+    "slio_s2m_kf_push": (C.c_int, [_P, _FP, _FP, _FP, C.c_int64, _IP]),
+    "slio_s2m_kf_push_scan": (C.c_int, [_P, _IP]),
+    "slio_s2m_kf_info": (C.c_int, [_P, _IP, _I64P]),
+    "slio_s2m_kf_sizes": (C.c_int, [_P, _I64P, C.c_int64]),
+    "slio_s2m_kf_clear": (C.c_int, [_P]),
+    "slio_s2m_kf_get": (C.c_int, [_P, C.c_int32, _FP, _FP, _FP, C.c_int64, _I64P]),
+    "slio_s2m_map_from_keyframes": (C.c_int, [_P, _IP, _FP, C.c_int32, C.c_float, _I64P]),
     "slio_scan_upload_voxel": (C.c_int, [_P, _FP, _FP, _FP, C.c_int64, C.c_float, _I64P]),
     "slio_scan_download": (C.c_int, [_P, _FP, _FP, _FP]),
     "slio_map_add_points": (C.c_int, [_P, _FP, _FP, _FP, C.c_int64, C.c_int, C.c_float, _I64P]),

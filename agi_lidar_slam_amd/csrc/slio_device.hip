@@ -3777,6 +3777,15 @@ struct Ctx {
                               // (zero between launches)
   MapDev::Buf pre[16];        // undistortion / VoxelGrid temporaries, kept across scans
                               // (per-call hipMalloc + hipFree cost more than the kernels)
+  // LIO-SAM keyframe store (slio_s2m_kf_*): one growing SoA arena, keyframe k
+  // at [kf_off[k], kf_off[k] + kf_len[k])
+  float* kfx = nullptr;
+  float* kfy = nullptr;
+  float* kfz = nullptr;
+  int64_t kf_used = 0, kf_cap = 0;
+  std::vector<int64_t> kf_off, kf_len;
+  MapDev::Buf kfb[3];         // map assembly: the concatenation (SoA), the segment table,
+                              // build_index's input; kept across scans
   IkfCtl* ctl = nullptr;    // device-resident update state (HBM)
   IkfCtl* h_ctl = nullptr;  // mapped, coherent host block: update input and output
   IkfCtl* d_hctl = nullptr; // its device view
@@ -4535,6 +4544,10 @@ int slio_destroy(slio_handle h) {
     if (b.p) (void)hipFree(b.p);
   for (auto& b : h->c.pre)
     if (b.p) (void)hipFree(b.p);
+  for (auto& b : h->c.kfb)
+    if (b.p) (void)hipFree(b.p);
+  for (float* q : {h->c.kfx, h->c.kfy, h->c.kfz})
+    if (q) (void)hipFree(q);
   if (h->c.comm) (void)ncclCommDestroy((ncclComm_t)h->c.comm);
   if (h->c.grp_ev) (void)hipEventDestroy(h->c.grp_ev);
   (void)hipFree(h->c.gsup);
@@ -5835,6 +5848,161 @@ __global__ void k_vg_centroids(const float* __restrict__ x, const float* __restr
   oz[r] = sz / cnt;
 }
 
+// workgroup -> grid reduction of a box in fkey order (and a count) as
+// k_vg_bbox does it: shuffles, then one set of atomics per workgroup.  Every
+// thread of the workgroup must call it.
+__device__ __forceinline__ void vg_box_reduce(int32_t lo[3], int32_t hi[3], int cnt, int32_t* __restrict__ out) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    for (int d = 32; d > 0; d >>= 1) {
+      lo[a] = min(lo[a], __shfl_xor(lo[a], d, 64));
+      hi[a] = max(hi[a], __shfl_xor(hi[a], d, 64));
+    }
+  for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+  __shared__ int32_t wl[3][4], wh[3][4];
+  __shared__ int wc[4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      wl[a][w] = lo[a];
+      wh[a][w] = hi[a];
+    }
+    wc[w] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int a = threadIdx.x;
+    int32_t l = wl[a][0], h = wh[a][0];
+    for (int q = 1; q < (int)(blockDim.x >> 6); ++q) {
+      l = min(l, wl[a][q]);
+      h = max(h, wh[a][q]);
+    }
+    atomicMin(out + a, l);
+    atomicMax(out + 3 + a, h);
+  } else if (threadIdx.x == 3) {
+    int c = 0;
+    for (int q = 0; q < (int)(blockDim.x >> 6); ++q) c += wc[q];
+    atomicAdd(out + 6, c);
+  }
+}
+
+// k_vg_centroids for the keyframe map assembly: the centroid goes out as
+// {x, y, z, bits(id)}, id = its rank in the output order, straight into
+// build_index's input, and the output's box is folded into obb (fkey order)
+// so the map's grid needs no further pass.  With either geometry flag set
+// (no finite point / pass-through) the keys are meaningless: nothing is done.
+__global__ void __launch_bounds__(256)
+k_vg_centroids4(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+                const uint32_t* __restrict__ keys, const uint32_t* __restrict__ order,
+                const uint32_t* __restrict__ head, const uint32_t* __restrict__ rank, int64_t n,
+                const uint32_t* __restrict__ flags, float4* __restrict__ out, int32_t* __restrict__ obb) {
+  if (flags[0] | flags[1]) return;  // (uniform)
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+  int cnt1 = 0;
+  if (i0 < n && head[i0]) {
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    int64_t j = i0;
+    for (; j < n && keys[j] == keys[i0]; ++j) {
+      const uint32_t o = order[j];
+      sx = sx + x[o];
+      sy = sy + y[o];
+      sz = sz + z[o];
+    }
+    const float cnt = (float)(j - i0);
+    const uint32_t r = rank[i0];
+    const float c[3] = {sx / cnt, sy / cnt, sz / cnt};
+    out[r] = make_float4(c[0], c[1], c[2], __uint_as_float(r));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = fkey(c[a]);
+    cnt1 = 1;
+  }
+  vg_box_reduce(lo, hi, cnt1, obb);
+}
+
+// ---------------------------------------------------------------- keyframe map assembly
+// LIO-SAM extractCloud (mapOptmization.cpp:1204-1251): every selected
+// keyframe's cloud through transformPointCloud (:382-409) into one
+// concatenation, in ONE launch.  The keyframes live in the handle's SoA
+// arena; seg[s] describes the s-th NON-EMPTY selected entry: its first
+// position in the concatenation, its first position in the arena and the
+// float affine of its pose (pcl::getTransformation, host).
+struct KfSeg {
+  int64_t start;  // arena position of the keyframe's first point
+  uint32_t off;   // concatenation position of the entry's first point
+  uint32_t pad;
+  float m[12];
+};
+constexpr int kKfTile = 256;
+
+// Each workgroup takes tiles of kKfTile consecutive concatenation positions;
+// the segments a tile touches (at most kKfTile: none is empty) are staged in
+// LDS and each thread finds its own by bisection there.  World point =
+// m0 x + m1 y + m2 z + m3, left to right (:400-405; the build has
+// -ffp-contract=off).  The VoxelGrid box and finite count of the
+// concatenation (k_vg_bbox's work) are folded in: one set of atomics per
+// workgroup.
+__global__ void __launch_bounds__(kKfTile)
+k_kf_gather(const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
+            const KfSeg* __restrict__ seg, int nseg, int64_t n, float* __restrict__ cx,
+            float* __restrict__ cy, float* __restrict__ cz, int32_t* __restrict__ bb) {
+  __shared__ KfSeg ls[kKfTile];
+  int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+  int cnt = 0;
+  const int64_t ntiles = (n + kKfTile - 1) / kKfTile;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t i0 = t * kKfTile, i1 = min(i0 + (int64_t)kKfTile, n) - 1;
+    // last segment starting at or before i0 / i1 (seg[0].off == 0)
+    int s0, s1;
+    {
+      int a = 0, b = nseg - 1;
+      while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if ((int64_t)seg[mid].off <= i0) a = mid; else b = mid - 1;
+      }
+      s0 = a;
+      b = min(nseg - 1, s0 + kKfTile - 1);
+      while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if ((int64_t)seg[mid].off <= i1) a = mid; else b = mid - 1;
+      }
+      s1 = a;
+    }
+    const int ns = s1 - s0 + 1;  // 1..kKfTile
+    __syncthreads();             // the previous tile's readers are done
+    if ((int)threadIdx.x < ns) ls[threadIdx.x] = seg[s0 + threadIdx.x];
+    __syncthreads();
+    const int64_t i = i0 + threadIdx.x;
+    if (i <= i1) {
+      int a = 0, b = ns - 1;
+      while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if ((int64_t)ls[mid].off <= i) a = mid; else b = mid - 1;
+      }
+      const KfSeg& S = ls[a];
+      const int64_t j = S.start + (i - (int64_t)S.off);
+      const float x = ax[j], y = ay[j], z = az[j];
+      const float w[3] = {((S.m[0] * x + S.m[1] * y) + S.m[2] * z) + S.m[3],
+                          ((S.m[4] * x + S.m[5] * y) + S.m[6] * z) + S.m[7],
+                          ((S.m[8] * x + S.m[9] * y) + S.m[10] * z) + S.m[11]};
+      cx[i] = w[0];
+      cy[i] = w[1];
+      cz[i] = w[2];
+      if (isfinite(w[0]) && isfinite(w[1]) && isfinite(w[2])) {  // getMinMax3D skips the others
+        ++cnt;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const int32_t k = fkey(w[q]);
+          lo[q] = min(lo[q], k);
+          hi[q] = max(hi[q], k);
+        }
+      }
+    }
+  }
+  vg_box_reduce(lo, hi, cnt, bb);
+}
+
 // exclusive scan of n flags into rank, enqueued on st (no readback)
 static int scan_launch(const uint32_t* flag, uint32_t* rank, int64_t n, hipStream_t st) {
   size_t tb = 0;
@@ -7073,12 +7241,79 @@ int slio_fov_segment(const double pos_lid[3], float box_min[3], float box_max[3]
 
 }  // extern "C"
 
+// The VoxelGrid work the scan's downSizeFilterSurf and the keyframe map
+// assembly (slio_s2m_map_from_keyframes) share: vg_begin takes the cached
+// temporaries and resets the boxes, vg_enqueue runs box -> geometry -> voxel
+// keys -> sort -> voxel heads -> ranks.  Everything is enqueued on the handle's
+// stream; nothing is read back here.
+struct VgWork {
+  uint32_t *k0, *k1, *v0, *v1, *hd, *rk;
+  int32_t* bb;       // input box keys [0..5], finite points [6]
+  int32_t* obb;      // bb + 8: output box keys [0..5] (k_vg_centroids4)
+  VgGeom* geom;
+  uint32_t* vflags;  // [0] no finite point, [1] leaf too small (pass-through)
+  MapDev::Buf* sort_tmp;
+};
+
+static int vg_begin(Ctx& c, int64_t n, const char* who, VgWork& w) {
+  hipError_t e;
+  // (pre[0..3] may hold the undistorted input: slio_scan_upload_undistort_voxel)
+  MapDev::Buf* B = c.pre + 8;
+  if ((e = MapDev::take(B[0], 4 * n)) || (e = MapDev::take(B[1], 4 * n)) || (e = MapDev::take(B[2], 4 * n)) ||
+      (e = MapDev::take(B[3], 4 * n)) || (e = MapDev::take(B[4], 4 * n)) || (e = MapDev::take(B[5], 4 * n)) ||
+      (e = MapDev::take(B[6], 64 + sizeof(VgGeom) + 8))) {
+    set_error(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+    return SLIO_ENOMEM;
+  }
+  w.k0 = (uint32_t*)B[0].p;
+  w.k1 = (uint32_t*)B[1].p;
+  w.v0 = (uint32_t*)B[2].p;
+  w.v1 = (uint32_t*)B[3].p;
+  w.hd = (uint32_t*)B[4].p;
+  w.rk = (uint32_t*)B[5].p;
+  w.bb = (int32_t*)B[6].p;
+  w.obb = w.bb + 8;
+  w.geom = reinterpret_cast<VgGeom*>((char*)B[6].p + 64);
+  w.vflags = reinterpret_cast<uint32_t*>((char*)B[6].p + 64 + sizeof(VgGeom));
+  w.sort_tmp = &B[7];
+  // (both boxes in one copy: the scan path pays what it paid for one)
+  const int32_t init[16] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0, 0,
+                            INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0, 0};
+  if ((e = hipMemcpyAsync(w.bb, init, 64, hipMemcpyHostToDevice, c.stream))) {
+    set_error(std::string(who) + ": H2D: " + hipGetErrorString(e));
+    return SLIO_EDEVICE;
+  }
+  return SLIO_OK;
+}
+
+// box_done: the caller's kernel has already folded the box and the finite
+// count into w.bb (k_kf_gather), so the cloud is not read for them again
+static int vg_enqueue(Ctx& c, const VgWork& w, const float* dx_, const float* dy_, const float* dz_, int64_t n,
+                      float leaf, bool box_done, const char* who) {
+  hipStream_t st = c.stream;
+  hipError_t e;
+  // the box, the geometry and the voxel keys stay on the device: the caller
+  // makes ONE readback (voxel count and the geometry's flags) where the box
+  // used to come back first
+  if (!box_done) k_vg_bbox<<<std::min(grid_blocks(n), 64), 256, 0, st>>>(dx_, dy_, dz_, n, w.bb);
+  k_vg_geom<<<1, 64, 0, st>>>(w.bb, leaf, w.geom, w.vflags);
+  const int nb = grid_blocks(n);
+  k_vg_keys<<<nb, 256, 0, st>>>(dx_, dy_, dz_, n, w.geom, w.k0, w.v0);
+  size_t tb = 0;
+  if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, w.k0, w.k1, w.v0, w.v1, (int)n, 0, 32, st)) ||
+      (e = MapDev::take(*w.sort_tmp, tb)) ||
+      (e = hipcub::DeviceRadixSort::SortPairs(w.sort_tmp->p, tb, w.k0, w.k1, w.v0, w.v1, (int)n, 0, 32, st))) {
+    set_error(std::string(who) + ": sort: " + hipGetErrorString(e));
+    return SLIO_EDEVICE;
+  }
+  k_vg_heads<<<nb, 256, 0, st>>>(w.k1, n, w.hd);
+  return scan_launch(w.hd, w.rk, n, st);
+}
+
 // downSizeFilterSurf of n device points (dx_, dy_, dz_) into the handle's scan
 static int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float* dz_, int64_t n, float leaf,
                         int64_t* n_down) {
   hipStream_t st = c.stream;
-  uint32_t *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr, *hd = nullptr, *rk = nullptr;
-  int32_t* bb = nullptr;
   int rc = nbr_settle_shared(c);  // the scan it was searched with is replaced
   if (rc) return rc;
   int64_t m = 0;
@@ -7086,50 +7321,12 @@ static int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float*
   do {
     if (n == 0) break;
     hipError_t e;
-    // (pre[0..3] may hold the undistorted input: slio_scan_upload_undistort_voxel)
-    MapDev::Buf* B = c.pre + 8;
-    if ((e = MapDev::take(B[0], 4 * n)) || (e = MapDev::take(B[1], 4 * n)) || (e = MapDev::take(B[2], 4 * n)) ||
-        (e = MapDev::take(B[3], 4 * n)) || (e = MapDev::take(B[4], 4 * n)) || (e = MapDev::take(B[5], 4 * n)) ||
-        (e = MapDev::take(B[6], 32 + sizeof(VgGeom) + 8))) {
-      set_error(std::string("slio_scan_upload_voxel: hipMalloc: ") + hipGetErrorString(e));
-      rc = SLIO_ENOMEM;
-      break;
-    }
-    k0 = (uint32_t*)B[0].p;
-    k1 = (uint32_t*)B[1].p;
-    v0 = (uint32_t*)B[2].p;
-    v1 = (uint32_t*)B[3].p;
-    hd = (uint32_t*)B[4].p;
-    rk = (uint32_t*)B[5].p;
-    bb = (int32_t*)B[6].p;
-    const int32_t init[8] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0, 0};
-    if ((e = hipMemcpyAsync(bb, init, 32, hipMemcpyHostToDevice, st))) {
-      set_error(std::string("slio_scan_upload_voxel: H2D: ") + hipGetErrorString(e));
-      rc = SLIO_EDEVICE;
-      break;
-    }
-    // the box, the geometry and the voxel keys stay on the device: ONE
-    // readback below (voxel count and the geometry's flags) where the box used
-    // to come back first
-    VgGeom* gdev = reinterpret_cast<VgGeom*>((char*)B[6].p + 32);
-    uint32_t* vflags = reinterpret_cast<uint32_t*>((char*)B[6].p + 32 + sizeof(VgGeom));
-    k_vg_bbox<<<std::min(grid_blocks(n), 64), 256, 0, st>>>(dx_, dy_, dz_, n, bb);
-    k_vg_geom<<<1, 64, 0, st>>>(bb, leaf, gdev, vflags);
-    const int nb = grid_blocks(n);
-    k_vg_keys<<<nb, 256, 0, st>>>(dx_, dy_, dz_, n, gdev, k0, v0);
-    size_t tb = 0;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0, k1, v0, v1, (int)n, 0, 32, st)) ||
-        (e = MapDev::take(B[7], tb)) ||
-        (e = hipcub::DeviceRadixSort::SortPairs(B[7].p, tb, k0, k1, v0, v1, (int)n, 0, 32, st))) {
-      set_error(std::string("slio_scan_upload_voxel: sort: ") + hipGetErrorString(e));
-      rc = SLIO_EDEVICE;
-      break;
-    }
-    k_vg_heads<<<nb, 256, 0, st>>>(k1, n, hd);
-    if ((rc = scan_launch(hd, rk, n, st))) break;
+    VgWork w{};
+    if ((rc = vg_begin(c, n, "slio_scan_upload_voxel", w))) break;
+    if ((rc = vg_enqueue(c, w, dx_, dy_, dz_, n, leaf, false, "slio_scan_upload_voxel"))) break;
     uint32_t got[4] = {0, 0, 0, 0};
     {
-      const Rb rb[3] = {{&got[0], rk + n - 1, 4}, {&got[1], hd + n - 1, 4}, {&got[2], vflags, 8}};
+      const Rb rb[3] = {{&got[0], w.rk + n - 1, 4}, {&got[1], w.hd + n - 1, 4}, {&got[2], w.vflags, 8}};
       if ((e = readback(st, rb, 3))) {
         set_error(std::string("slio_scan_upload_voxel: counts: ") + hipGetErrorString(e));
         rc = SLIO_EDEVICE;
@@ -7148,7 +7345,7 @@ static int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float*
       break;
     }
     if ((rc = ensure_scan_buffers(c))) break;
-    k_vg_centroids<<<nb, 256, 0, st>>>(dx_, dy_, dz_, k1, v1, hd, rk, n, c.bx, c.by, c.bz);
+    k_vg_centroids<<<grid_blocks(n), 256, 0, st>>>(dx_, dy_, dz_, w.k1, w.v1, w.hd, w.rk, n, c.bx, c.by, c.bz);
     if ((e = hipGetLastError())) {
       set_error(std::string("slio_scan_upload_voxel: ") + hipGetErrorString(e));
       rc = SLIO_EDEVICE;
@@ -7903,6 +8100,283 @@ int slio_iterate_async(slio_handle h, const slio_pose* x, int do_search, int ext
   const int rc = enqueue_pass(c, &P, nullptr, do_search ? 1 : 0, extrinsic_est);
   if (rc) return rc;
   if (d_super) *d_super = c.d_super;
+  return SLIO_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- LIO-SAM keyframe store and local map
+// saveKeyFramesAndFactor's cornerCloudKeyFrames / surfCloudKeyFrames
+// (mapOptmization.cpp:2069-2077) and extractCloud (:1204-1251) on the device.
+
+// room for n more points in the arena (grown by half, the stored keyframes
+// copied on the stream; hipFree waits for the copy)
+static int kf_reserve(Ctx& c, int64_t n, const char* who) {
+  if (c.kf_used + n <= c.kf_cap) return SLIO_OK;
+  const int64_t cap = std::max<int64_t>(c.kf_used + n + (c.kf_used + n) / 2, 1 << 16);
+  float* q[3] = {nullptr, nullptr, nullptr};
+  float* const old[3] = {c.kfx, c.kfy, c.kfz};
+  hipError_t e = hipSuccess;
+  for (int a = 0; a < 3 && !e; ++a) {
+    e = hipMalloc(&q[a], 4 * cap);
+    if (!e && c.kf_used > 0) e = hipMemcpyAsync(q[a], old[a], 4 * c.kf_used, hipMemcpyDeviceToDevice, c.stream);
+  }
+  if (!e) e = hipStreamSynchronize(c.stream);
+  if (e) {
+    (void)hipGetLastError();
+    for (float* p : q)
+      if (p) (void)hipFree(p);
+    set_error(std::string(who) + ": keyframe arena: " + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? SLIO_ENOMEM : SLIO_EDEVICE;
+  }
+  for (float* p : old)
+    if (p) (void)hipFree(p);
+  c.kfx = q[0];
+  c.kfy = q[1];
+  c.kfz = q[2];
+  c.kf_cap = cap;
+  return SLIO_OK;
+}
+
+static void kf_append(Ctx& c, int64_t n, int32_t* key_index) {
+  if (key_index) *key_index = (int32_t)c.kf_off.size();
+  c.kf_off.push_back(c.kf_used);
+  c.kf_len.push_back(n);
+  c.kf_used += n;
+}
+
+#define SLIO_KF_ARGS(cond, who)                  \
+  do {                                           \
+    if (!h) {                                    \
+      set_error("null handle");                  \
+      return SLIO_EINVAL;                        \
+    }                                            \
+    if (cond) {                                  \
+      set_error(who ": bad arguments");          \
+      return SLIO_EINVAL;                        \
+    }                                            \
+  } while (0)
+
+extern "C" {
+
+int slio_s2m_kf_push(slio_handle h, const float* x, const float* y, const float* z, int64_t n,
+                     int32_t* key_index) {
+  SLIO_KF_ARGS(n < 0 || (n > 0 && (!x || !y || !z)) || n > INT32_MAX, "slio_s2m_kf_push");
+  Ctx& c = h->c;
+  if (c.kf_off.size() >= (size_t)INT32_MAX) {
+    set_error("slio_s2m_kf_push: too many keyframes");
+    return SLIO_ECAPACITY;
+  }
+  SLIO_HIP(hipSetDevice(c.prm.device));
+  if (n > 0) {
+    if (int rc = kf_reserve(c, n, "slio_s2m_kf_push")) return rc;
+    const int64_t o = c.kf_used;
+    SLIO_HIP(hipMemcpyAsync(c.kfx + o, x, 4 * n, hipMemcpyHostToDevice, c.stream));
+    SLIO_HIP(hipMemcpyAsync(c.kfy + o, y, 4 * n, hipMemcpyHostToDevice, c.stream));
+    SLIO_HIP(hipMemcpyAsync(c.kfz + o, z, 4 * n, hipMemcpyHostToDevice, c.stream));
+  }
+  kf_append(c, n, key_index);
+  return SLIO_OK;
+}
+
+int slio_s2m_kf_push_scan(slio_handle h, int32_t* key_index) {
+  SLIO_KF_ARGS(false, "slio_s2m_kf_push_scan");
+  Ctx& c = h->c;
+  if (!c.bx) {
+    set_error("slio_s2m_kf_push_scan: no scan uploaded");
+    return SLIO_ESTATE;
+  }
+  if (c.kf_off.size() >= (size_t)INT32_MAX) {
+    set_error("slio_s2m_kf_push_scan: too many keyframes");
+    return SLIO_ECAPACITY;
+  }
+  SLIO_HIP(hipSetDevice(c.prm.device));
+  const int64_t n = c.n;
+  if (n > 0) {
+    if (int rc = kf_reserve(c, n, "slio_s2m_kf_push_scan")) return rc;
+    const int64_t o = c.kf_used;
+    SLIO_HIP(hipMemcpyAsync(c.kfx + o, c.bx, 4 * n, hipMemcpyDeviceToDevice, c.stream));
+    SLIO_HIP(hipMemcpyAsync(c.kfy + o, c.by, 4 * n, hipMemcpyDeviceToDevice, c.stream));
+    SLIO_HIP(hipMemcpyAsync(c.kfz + o, c.bz, 4 * n, hipMemcpyDeviceToDevice, c.stream));
+  }
+  kf_append(c, n, key_index);
+  return SLIO_OK;
+}
+
+int slio_s2m_kf_info(slio_handle h, int32_t* nkeys, int64_t* npoints) {
+  SLIO_KF_ARGS(false, "slio_s2m_kf_info");
+  if (nkeys) *nkeys = (int32_t)h->c.kf_off.size();
+  if (npoints) *npoints = h->c.kf_used;
+  return SLIO_OK;
+}
+
+int slio_s2m_kf_sizes(slio_handle h, int64_t* sizes, int64_t cap) {
+  SLIO_KF_ARGS(cap < 0 || (cap > 0 && !sizes), "slio_s2m_kf_sizes");
+  const auto& len = h->c.kf_len;
+  if (cap < (int64_t)len.size()) {
+    set_error("slio_s2m_kf_sizes: buffer too small");
+    return SLIO_ECAPACITY;
+  }
+  for (size_t k = 0; k < len.size(); ++k) sizes[k] = len[k];
+  return SLIO_OK;
+}
+
+int slio_s2m_kf_clear(slio_handle h) {
+  SLIO_KF_ARGS(false, "slio_s2m_kf_clear");
+  // (the arena stays allocated; an assembly still in flight on the stream
+  // reads it before any later push writes it: one stream)
+  h->c.kf_off.clear();
+  h->c.kf_len.clear();
+  h->c.kf_used = 0;
+  return SLIO_OK;
+}
+
+int slio_s2m_kf_get(slio_handle h, int32_t key, float* x, float* y, float* z, int64_t cap, int64_t* n) {
+  SLIO_KF_ARGS(key < 0 || (size_t)key >= h->c.kf_off.size() || cap < 0, "slio_s2m_kf_get");
+  Ctx& c = h->c;
+  const int64_t len = c.kf_len[key], o = c.kf_off[key];
+  if (n) *n = len;
+  if (cap < len || (len > 0 && (!x || !y || !z))) {
+    set_error("slio_s2m_kf_get: buffer too small");
+    return SLIO_ECAPACITY;
+  }
+  if (len > 0) {
+    SLIO_HIP(hipSetDevice(c.prm.device));
+    SLIO_HIP(hipStreamSynchronize(c.stream));
+    SLIO_HIP(hipMemcpy(x, c.kfx + o, 4 * len, hipMemcpyDeviceToHost));
+    SLIO_HIP(hipMemcpy(y, c.kfy + o, 4 * len, hipMemcpyDeviceToHost));
+    SLIO_HIP(hipMemcpy(z, c.kfz + o, 4 * len, hipMemcpyDeviceToHost));
+  }
+  return SLIO_OK;
+}
+
+int slio_s2m_map_from_keyframes(slio_handle h, const int32_t* key_ind, const float* poses6, int32_t nsel,
+                                float leaf, int64_t counts[2]) {
+  static const char* who = "slio_s2m_map_from_keyframes";
+  SLIO_KF_ARGS(nsel < 0 || (nsel > 0 && (!key_ind || !poses6)) || !(leaf > 0.0f), "slio_s2m_map_from_keyframes");
+  Ctx& c = h->c;
+  // the segment table: non-empty entries only, so a tile of the gather
+  // touches at most one segment per point
+  std::vector<KfSeg> seg;
+  int64_t n = 0;
+  for (int32_t i = 0; i < nsel; ++i) {
+    const int32_t k = key_ind[i];
+    if (k < 0 || (size_t)k >= c.kf_off.size()) {
+      set_error(std::string(who) + ": key index " + std::to_string(k) + " out of range");
+      return SLIO_EINVAL;
+    }
+    if (c.kf_len[k] == 0) continue;
+    // the (int)n radix sorts of the VoxelGrid and of build_index
+    if (n + c.kf_len[k] > (int64_t)INT32_MAX) {
+      set_error(std::string(who) + ": more than 2^31 - 1 points selected");
+      return SLIO_ECAPACITY;
+    }
+    KfSeg s;
+    s.start = c.kf_off[k];
+    s.off = (uint32_t)n;
+    s.pad = 0;
+    const Aff12 T = s2m_affine(poses6 + 6 * (int64_t)i);
+    std::memcpy(s.m, T.m, sizeof(s.m));
+    seg.push_back(s);
+    n += c.kf_len[k];
+  }
+  SLIO_HIP(hipSetDevice(c.prm.device));
+  hipStream_t st = c.stream;
+  int rc = nbr_settle_shared(c);  // the map it was searched on is replaced
+  if (rc) return rc;
+  int64_t m = 0;
+  float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+  float4* in4 = nullptr;
+  if (n > 0) {
+    hipError_t e;
+    if ((e = MapDev::take(c.kfb[0], 12 * n)) || (e = MapDev::take(c.kfb[1], sizeof(KfSeg) * seg.size())) ||
+        (e = MapDev::take(c.kfb[2], 16 * n))) {
+      set_error(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+      return SLIO_ENOMEM;
+    }
+    float* cx = (float*)c.kfb[0].p;
+    float* cy = cx + n;
+    float* cz = cx + 2 * n;
+    KfSeg* dseg = (KfSeg*)c.kfb[1].p;
+    in4 = (float4*)c.kfb[2].p;
+    VgWork w{};
+    if ((rc = vg_begin(c, n, who, w))) return rc;
+    // (pageable source: the copy has left `seg` when the call returns)
+    SLIO_HIP(hipMemcpyAsync(dseg, seg.data(), sizeof(KfSeg) * seg.size(), hipMemcpyHostToDevice, st));
+    const int64_t ntiles = (n + kKfTile - 1) / kKfTile;
+    k_kf_gather<<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(c.kfx, c.kfy, c.kfz, dseg, (int)seg.size(),
+                                                                         n, cx, cy, cz, w.bb);
+    if ((rc = vg_enqueue(c, w, cx, cy, cz, n, leaf, true, who))) return rc;
+    // the centroids go out before the count is known (the output has room for
+    // n); then the call's ONE readback: voxel count, flags, both boxes
+    k_vg_centroids4<<<grid_blocks(n), 256, 0, st>>>(cx, cy, cz, w.k1, w.v1, w.hd, w.rk, n, w.vflags, in4, w.obb);
+    uint32_t got[4] = {0, 0, 0, 0};
+    int32_t boxes[16];  // the input's, then the output's
+    const int32_t *ibox = boxes, *obox = boxes + 8;
+    const Rb rb[4] = {{&got[0], w.rk + n - 1, 4}, {&got[1], w.hd + n - 1, 4}, {&got[2], w.vflags, 8},
+                      {boxes, w.bb, 64}};
+    if ((e = readback(st, rb, 4))) {
+      set_error(std::string(who) + ": counts: " + hipGetErrorString(e));
+      return SLIO_EDEVICE;
+    }
+    const int32_t* box = obox;
+    if (got[2]) {
+      m = 0;  // no finite point: empty map
+    } else if (got[3]) {
+      // PCL: leaf too small for the cloud, output = input (non-finite points
+      // stay, as in the scan path; the index clamps them into the grid)
+      m = n;
+      box = ibox;
+      k_pack_ids<<<grid_blocks(n), 256, 0, st>>>(cx, cy, cz, n, 0u, in4);
+    } else {
+      m = (int64_t)got[0] + got[1];
+    }
+    if (m > 0)
+      for (int a = 0; a < 3; ++a) {
+        mn[a] = fkey_inv(box[a]);
+        mx[a] = fkey_inv(box[3 + a]);
+      }
+  }
+  // The result becomes the handle's map as slio_map_upload's would.  A map
+  // only this handle holds is rebuilt in place, so its tables and
+  // build_index's temporaries are reused scan after scan; a shared one is
+  // left to its other users and this handle gets a new map.
+  const bool in_place = c.map && c.map.use_count() == 1 && c.map->users.size() == 1;
+  if (in_place) {
+    MapDev& M = *c.map;
+    std::unique_lock<std::shared_mutex> lk(M.mu);
+    if ((rc = map_write_begin(c))) return rc;
+    M.free_index();
+    M.nadd = 0;
+    M.next_id = (uint32_t)m;
+    M.cell0 = c.prm.grid_cell;
+    M.max_cells = c.prm.max_grid_cells;
+    rc = build_index(M, in4, m, mn, mx, st, who, false);
+    M.broken = rc != 0;
+    if (rc) M.free_index();
+    M.version++;
+    M.dirty = false;
+    const int rc2 = map_write_end(c);
+    if (rc || rc2) return rc ? rc : rc2;
+  } else {
+    auto M = std::make_shared<MapDev>();
+    M->device = c.prm.device;
+    M->cell0 = c.prm.grid_cell;
+    M->max_cells = c.prm.max_grid_cells;
+    M->next_id = (uint32_t)m;
+    if ((rc = build_index(*M, in4, m, mn, mx, st, who, false))) return rc;
+    // sharers of this map order their streams after its build
+    SLIO_HIP(hipEventCreateWithFlags(&M->ready, hipEventDisableTiming));
+    SLIO_HIP(hipEventRecord(M->ready, st));
+    M->epoch = 1;
+    map_attach(c, M);
+    c.seen_epoch = 1;
+  }
+  c.searched = false;
+  if (counts) {
+    counts[0] = n;
+    counts[1] = m;
+  }
   return SLIO_OK;
 }
 

@@ -6,9 +6,13 @@ surfOptimization (:1438-1515), combineOptimizationCoeffs (:1517-1543) and
 LMOptimization (:1552-1700).  The per-point work (pointAssociateToMap, exact
 5-NN in the corner / surf local maps, line and plane fits, the LM rows and
 the normal equations) runs on the device through libslio; the 6x6 step is
-host C++ (slio_s2m_lm_step).  transformUpdate's IMU blending (:1742-1781)
-and the keyframe / factor-graph back end are out of scope (SURVEY.md §8f-4
-names the scan-to-map core).
+host C++ (slio_s2m_lm_step).  The local map the solve runs against is made
+on the device too: the keyframe clouds (saveKeyFramesAndFactor :2069-2077)
+live in the handles' keyframe stores, downsampleCurrentScan (:1276-1288) and
+extractCloud (:1204-1251) run there, and extractNearby's key selection
+(:1152-1193, a few hundred poses) is host numpy (extract_nearby).
+transformUpdate's IMU blending (:1742-1781) and the factor graph are out of
+scope (SURVEY.md §8f-4 names the scan-to-map core).
 """
 from __future__ import annotations
 
@@ -20,6 +24,83 @@ from . import _lib as L
 
 EDGE_FEATURE_MIN_VALID_NUM = 10    # params.yaml edgeFeatureMinValidNum
 SURF_FEATURE_MIN_VALID_NUM = 100   # params.yaml surfFeatureMinValidNum
+
+
+def _pose_voxel_grid(pts: np.ndarray, leaf: float) -> np.ndarray:
+    """pcl::VoxelGrid of a few poses in float32 (PCL 1.10 applyFilter):
+    centroids in ascending voxel index, a voxel's points summed in input
+    order.  A leaf too small for the cloud passes it through."""
+    f = np.float32
+    if pts.shape[0] == 0:
+        return pts.copy()
+    inv = f(1.0) / f(leaf)
+    mn, mx = pts.min(axis=0), pts.max(axis=0)
+    min_b = np.floor(mn * inv).astype(np.int64)
+    max_b = np.floor(mx * inv).astype(np.int64)
+    d = ((mx - mn) * inv).astype(np.int64) + 1
+    if int(d[0]) * int(d[1]) * int(d[2]) > np.iinfo(np.int32).max:
+        return pts.copy()
+    div = max_b - min_b + 1
+    ijk = (np.floor(pts * inv) - min_b.astype(f)).astype(np.int64)
+    idx = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]
+    out = []
+    for v in np.unique(idx):
+        s = np.zeros(3, f)
+        members = np.nonzero(idx == v)[0]
+        for i in members:
+            s = s + pts[i]
+        out.append(s / f(len(members)))
+    return np.array(out, f).reshape(-1, 3)
+
+
+def extract_nearby(key_poses3d, key_times, t_cur: float, radius: float = 50.0, density: float = 2.0) -> np.ndarray:
+    """The keyframes extractNearby (:1152-1193) hands to extractCloud, after
+    extractCloud's own distance check (:1211), as a list of key indices for
+    ScanToMap.extract_cloud.  Host numpy: a few hundred poses.
+
+    key_poses3d (N, 3) = cloudKeyPoses3D, key_times (N,) = cloudKeyPoses6D's
+    stamps, t_cur = timeLaserInfoCur, radius = surroundingKeyframeSearchRadius,
+    density = surroundingKeyframeDensity.  Steps, in float32 as PCL:
+    the poses within `radius` of the last one in ascending distance (:1164-1172);
+    their VoxelGrid with leaf `density`, one centroid per voxel in ascending
+    voxel index (:1175-1176); each centroid replaced by the index of the key
+    pose nearest to it (:1179-1183); then the keys of the last 10 s, newest
+    first, appended with duplicates kept (:1186-1193).  An entry whose point --
+    the centroid, or the tail key's pose -- is farther than `radius` from the
+    last pose is dropped (:1211).
+
+    FLANN's order among poses at exactly equal distance (and whether a pose at
+    exactly `radius` counts) is not pinned by anything here: ties go to the
+    lower index, and the radius test is `<`.  Only the in-voxel summation
+    order, hence the last bits of a centroid, depends on it."""
+    f = np.float32
+    P = np.ascontiguousarray(np.asarray(key_poses3d, dtype=f).reshape(-1, 3))
+    T = np.asarray(key_times, dtype=np.float64).reshape(-1)
+    n = P.shape[0]
+    if n == 0:
+        return np.zeros(0, np.int32)
+
+    def sqd(a, b):
+        d = a - b
+        return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+    back = P[-1]
+    d2 = sqd(P, back)
+    near = np.nonzero(d2 < f(radius) * f(radius))[0]
+    near = near[np.argsort(d2[near], kind="stable")]
+    cents = _pose_voxel_grid(P[near], density)
+    keys, pts = [], []
+    for c in cents:
+        keys.append(int(np.argmin(sqd(P, c))))
+        pts.append(c)
+    for i in range(n - 1, -1, -1):
+        if t_cur - T[i] < 10.0:
+            keys.append(i)
+            pts.append(P[i])
+        else:
+            break
+    out = [k for k, p in zip(keys, pts) if not np.sqrt(sqd(np.asarray(p, f), back)) > f(radius)]
+    return np.array(out, np.int32)
 
 
 def _handle(max_points: int, grid_cell: float, device: int = 0):
@@ -72,6 +153,70 @@ class ScanToMap:
         """laserCloud{Corner,Surf}LastDS of the current frame."""
         self.n_corner = _upload(self.lib, self.lib.slio_scan_upload, self.hc, corner_last_ds)
         self.n_surf = _upload(self.lib, self.lib.slio_scan_upload, self.hs, surf_last_ds)
+
+    def downsample_current_scan(self, corner_last: np.ndarray, surf_last: np.ndarray,
+                                corner_leaf: float = 0.2, surf_leaf: float = 0.4):
+        """downsampleCurrentScan (:1276-1288): laserCloud{Corner,Surf}Last through
+        downSizeFilterCorner / downSizeFilterSurf (mappingCornerLeafSize 0.2,
+        mappingSurfLeafSize 0.4) on the device; the results are the handles'
+        scans (laserCloud*LastDS).  Returns their sizes."""
+        out = []
+        for h, pts, leaf in ((self.hc, corner_last, corner_leaf), (self.hs, surf_last, surf_leaf)):
+            pts = np.ascontiguousarray(np.asarray(pts, dtype=np.float32).reshape(-1, 3))
+            x, y, z = (np.ascontiguousarray(pts[:, k]) for k in range(3))
+            n = C.c_int64()
+            L.check(self.lib.slio_scan_upload_voxel(h, L.fptr(x), L.fptr(y), L.fptr(z), pts.shape[0], leaf,
+                                                    C.byref(n)), "downsampleCurrentScan")
+            out.append(n.value)
+        self.n_corner, self.n_surf = out
+        return self.n_corner, self.n_surf
+
+    def save_keyframe(self) -> int:
+        """saveKeyFramesAndFactor's cloud part (:2069-2077): the current
+        laserCloud{Corner,Surf}LastDS become the next keyframe's clouds (device
+        to device).  Returns the keyframe's index."""
+        kc, ks = C.c_int32(), C.c_int32()
+        L.check(self.lib.slio_s2m_kf_push_scan(self.hc, C.byref(kc)), "save_keyframe (corner)")
+        L.check(self.lib.slio_s2m_kf_push_scan(self.hs, C.byref(ks)), "save_keyframe (surf)")
+        if kc.value != ks.value:
+            raise L.SlioError(f"save_keyframe: corner / surf stores out of step ({kc.value} / {ks.value})")
+        return kc.value
+
+    def push_keyframe(self, corner: np.ndarray, surf: np.ndarray) -> int:
+        """A keyframe from host clouds in the LiDAR frame (e.g. a saved map)."""
+        keys = []
+        for h, pts in ((self.hc, corner), (self.hs, surf)):
+            pts = np.ascontiguousarray(np.asarray(pts, dtype=np.float32).reshape(-1, 3))
+            x, y, z = (np.ascontiguousarray(pts[:, k]) for k in range(3))
+            k = C.c_int32()
+            L.check(self.lib.slio_s2m_kf_push(h, L.fptr(x), L.fptr(y), L.fptr(z), pts.shape[0], C.byref(k)),
+                    "push_keyframe")
+            keys.append(k.value)
+        if keys[0] != keys[1]:
+            raise L.SlioError(f"push_keyframe: corner / surf stores out of step ({keys[0]} / {keys[1]})")
+        return keys[0]
+
+    def extract_cloud(self, key_ind, poses6, corner_leaf: float = 0.2, surf_leaf: float = 0.4):
+        """extractCloud (:1204-1251): keyframes key_ind[i] at poses6[i] (roll,
+        pitch, yaw, x, y, z) transformed, concatenated in list order and
+        downsampled into laserCloud{Corner,Surf}FromMapDS, which become the
+        handles' maps -- all on the device.  Returns ((corner points
+        concatenated, corner map points), (surf ..., surf ...))."""
+        key = np.ascontiguousarray(np.asarray(key_ind, dtype=np.int32).reshape(-1))
+        poses = np.ascontiguousarray(np.asarray(poses6, dtype=np.float32).reshape(-1, 6))
+        if poses.shape[0] != key.shape[0]:
+            raise ValueError("extract_cloud: one pose per selected keyframe")
+        out = []
+        for h, leaf in ((self.hc, corner_leaf), (self.hs, surf_leaf)):
+            cnt = np.zeros(2, np.int64)
+            L.check(self.lib.slio_s2m_map_from_keyframes(h, L.iptr(key), L.fptr(poses), key.shape[0], leaf,
+                                                         L.i64ptr(cnt)), "extractCloud")
+            out.append((int(cnt[0]), int(cnt[1])))
+        return tuple(out)
+
+    def clear_keyframes(self) -> None:
+        for h in (self.hc, self.hs):
+            L.check(self.lib.slio_s2m_kf_clear(h), "clear_keyframes")
 
     def corner_optimization(self, transform: np.ndarray, count: bool = True) -> int:
         """:1303-1432; count: return the selected points (a device -> host

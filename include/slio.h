@@ -451,6 +451,57 @@ int slio_s2m_normal_equations(slio_handle h_corner, slio_handle h_surf,
 int slio_s2m_lm_step(const float AtA[36], const float AtB[6], int64_t nsel, int iter_count,
                      float transform[6], int* is_degenerate, float matP[36], int* converged);
 
+/* -- keyframe store and local map (extractSurroundingKeyFrames, :1152-1270) --
+ * Each handle keeps the keyframe clouds of its feature class
+ * (cornerCloudKeyFrames / surfCloudKeyFrames, :2069-2077) in device memory,
+ * in the LiDAR frame, numbered 0, 1, ... in push order.  Argument errors
+ * (null handle, negative sizes, a key out of range) are reported before any
+ * device call. */
+/* cornerCloudKeyFrames.push_back (:2076-2077) of a host cloud (SoA float32,
+ * n points; n == 0 is a valid keyframe); *key_index = its number. */
+int slio_s2m_kf_push(slio_handle h, const float* x, const float* y, const float* z,
+                     int64_t n, int32_t* key_index);
+/* saveKeyFramesAndFactor's copy of laserCloud{Corner,Surf}LastDS (:2069-2077):
+ * the handle's current scan becomes a keyframe by a device-to-device copy.
+ * ESTATE when the handle has no scan. */
+int slio_s2m_kf_push_scan(slio_handle h, int32_t* key_index);
+/* Number of keyframes (cloudKeyPoses3D->size(), :1159) and of stored points. */
+int slio_s2m_kf_info(slio_handle h, int32_t* nkeys, int64_t* npoints);
+/* Points per keyframe, sizes[0..nkeys); ECAPACITY if cap < nkeys. */
+int slio_s2m_kf_sizes(slio_handle h, int64_t* sizes, int64_t cap);
+/* Forget every keyframe; numbering restarts at 0 (the reference never drops
+ * a keyframe cloud: for a new session or a bounded store). */
+int slio_s2m_kf_clear(slio_handle h);
+/* Keyframe `key` back to the host (tests, saveMapService :486); cap is
+ * the buffers' length, *n the keyframe's size (ECAPACITY if cap is smaller). */
+int slio_s2m_kf_get(slio_handle h, int32_t key, float* x, float* y, float* z,
+                    int64_t cap, int64_t* n);
+/* extractCloud (:1204-1251) on the device.  For i in list order keyframe
+ * key_ind[i] goes through transformPointCloud (:382-409) with the pose
+ * poses6[6 i ..] = {roll, pitch, yaw, x, y, z} -- pcl::getTransformation in
+ * float, then m0 x + m1 y + m2 z + m3 per row, left to right (:389-405) --
+ * and the clouds are concatenated in list order (a key may repeat:
+ * extractNearby :1186-1193 appends the recent keyframes without looking for
+ * duplicates).  The concatenation is then downsampled with edge `leaf`
+ * (downSizeFilterCorner / downSizeFilterSurf, :1242-1247) under the semantics
+ * of slio_scan_upload_voxel: non-finite points dropped, inside a voxel the
+ * points summed in ascending position of the concatenation, a leaf too small
+ * for the cloud passes the concatenation through, no finite point gives an
+ * empty map.  The result becomes the handle's map exactly as slio_map_upload
+ * of those points would make it (ids 0..n-1 in output order, the kd-tree
+ * rebuild of :1716-1717), without a point travelling to the host: the host
+ * waits once, for the voxel count, the flags and the box the grid needs, and
+ * then as slio_map_upload does for the index build.  counts = {points
+ * concatenated, map points}.  EINVAL for a key out of range, ECAPACITY for
+ * more than 2^31 - 1 selected points (the concatenation is not bounded by
+ * max_points, which is the scan's capacity); nsel == 0 gives an empty map.
+ * The reference's laserCloudMapContainer (:1219-1237, 1250), a cache of transformed
+ * keyframes, is not mirrored: the same pose gives the same floats, and
+ * transforming a keyframe again reads no more bytes than copying its cached
+ * transform would. */
+int slio_s2m_map_from_keyframes(slio_handle h, const int32_t* key_ind, const float* poses6,
+                                int32_t nsel, float leaf, int64_t counts[2]);
+
 /* Manifold helpers exported for tests (esekfom.hpp:59-73, 236-258). */
 int slio_state_boxplus(const slio_state* x, const double dx[24], slio_state* out);
 int slio_state_boxminus(const slio_state* x1, const slio_state* x2, double dx[24]);

@@ -7,6 +7,9 @@
   preproc   UndistortPcl back-propagation + downSizeFilterSurf of a raw scan
   s2m       one LIO-SAM scan-to-map iteration (corner + surf coefficients, normal
             equations, LM step)
+  s2m_map   one LIO-SAM local-map assembly (extractCloud) of 50 keyframes from the
+            device keyframe store, against the host path it replaces (only when
+            named: it also runs the CPU oracle)
 One JSON line per measurement (host wall clock around synchronous calls)."""
 import ctypes as C
 import json
@@ -196,8 +199,66 @@ def s2m():
     s.close()
 
 
+def s2m_map(n_kf=50, n_surf=20000, n_corner=1000, reps=200):
+    """One local-map assembly per scan (extractCloud): n_kf keyframes of
+    n_surf surf and n_corner corner points (drawn from the synthetic scene
+    with 5 cm noise, each in the LiDAR frame of its own pose), leaves 0.4 /
+    0.2, on the device from the keyframe store -- against the host path
+    set_maps replaces: the oracle's transformPointCloud + VoxelGrid on the CPU
+    (single thread), then slio_map_upload of both maps."""
+    from agi_lidar_slam_amd import synth
+    from agi_lidar_slam_amd.lio_sam import ScanToMap
+    from oracle import oracle as O
+    O.build()
+    pr = synth.make_s2m_problem()
+    rng = np.random.default_rng(7)
+    s = ScanToMap(max_points=60000)
+    kfs, poses = [], []
+    for k in range(n_kf):
+        pose = np.array([0.002 * k, -0.003 * k, 0.02 * k, 0.5 * k, -0.1 * k, 0.01 * k], np.float32)
+        cr, sr, cp, sp, cy, sy = (f(float(a)) for a in pose[:3] for f in (np.cos, np.sin))
+        R = np.array([[cy * cp, cy * sp * sr - sy * cr, sy * sr + cy * sp * cr],
+                      [sy * cp, cy * cr + sy * sp * sr, sy * sp * cr - cy * sr], [-sp, cp * sr, cp * cr]])
+        out = []
+        for mp, n in ((pr["corner_map"], n_corner), (pr["surf_map"], n_surf)):
+            w = mp[rng.choice(mp.shape[0], n)] + rng.normal(0, 0.05, (n, 3))
+            out.append(((w - pose[3:].astype(np.float64)) @ R).astype(np.float32))
+        kfs.append(out)
+        poses.append(pose)
+        s.push_keyframe(out[0], out[1])
+    poses = np.stack(poses)
+    keys = np.arange(n_kf, dtype=np.int32)
+
+    def device():
+        return s.extract_cloud(keys, poses)   # (each call waits for its index build)
+    first, _ = t_ms(device)
+    ms_dev, cnt = t_ms(device, reps)
+    host = {}
+
+    def host_path():
+        t0 = time.perf_counter()
+        cats = [np.concatenate([O.s2m_transform(poses[k], kfs[k][j]) for k in range(n_kf)]) for j in range(2)]
+        t1 = time.perf_counter()
+        maps = [O.voxel_grid(cats[0], 0.2), O.voxel_grid(cats[1], 0.4)]
+        t2 = time.perf_counter()
+        s.set_maps(maps[0], maps[1])
+        t3 = time.perf_counter()
+        host.update(ms_transform=(t1 - t0) * 1e3, ms_voxel_grid=(t2 - t1) * 1e3, ms_map_upload=(t3 - t2) * 1e3,
+                    map_points=[int(m.shape[0]) for m in maps])
+    host_path()
+    ms_host, _ = t_ms(host_path, 3)
+    print(json.dumps({"bench": "lio_sam_s2m_map_assembly", "keyframes": n_kf, "surf_points_per_keyframe": n_surf,
+                      "corner_points_per_keyframe": n_corner, "concatenated_corner_surf": [cnt[0][0], cnt[1][0]],
+                      "map_points_corner_surf": [cnt[0][1], cnt[1][1]], "ms_device_first_call": first,
+                      "ms_device_per_scan": ms_dev, "ms_host_path_per_scan": ms_host,
+                      "host_path_last": host}), flush=True)
+    s.close()
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "s2m_map" in what:
+        s2m_map()
     if "mapping" in what:
         mapping(10_000_000, 100_000)
     if "chain" in what:
