@@ -164,6 +164,21 @@ class SlioImuPose(C.Structure):
                 ("vel", C.c_double * 3), ("pos", C.c_double * 3), ("rot", C.c_double * 9)]
 
 
+class SlioIcpParams(C.Structure):
+    """slio_icp_params (include/slio.h)."""
+    _fields_ = [("max_iterations", C.c_int32), ("reserved", C.c_int32),
+                ("transformation_epsilon", C.c_double), ("euclidean_fitness_epsilon", C.c_double)]
+
+
+class SlioIcpState(C.Structure):
+    """slio_icp_state (include/slio.h)."""
+    _fields_ = [("final_T", C.c_float * 16), ("prev_mse", C.c_double), ("iterations", C.c_int32),
+                ("similar", C.c_int32), ("convergence_state", C.c_int32), ("converged", C.c_int32)]
+
+
+# DefaultConvergenceCriteria::ConvergenceState (SLIO_ICP_*)
+ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
+
 SLIO_COMM_ID_BYTES = 128
 SLIO_GROUP_RCCL = 1
 SLIO_GROUP_DEVICE = 2
@@ -203,6 +218,14 @@ SIGNATURES = {
     "slio_s2m_kf_clear": (C.c_int, [_P]),
     "slio_s2m_kf_get": (C.c_int, [_P, C.c_int32, _FP, _FP, _FP, C.c_int64, _I64P]),
     "slio_s2m_map_from_keyframes": (C.c_int, [_P, _IP, _FP, C.c_int32, C.c_float, _I64P]),
+    "slio_s2m_loop_cloud": (C.c_int, [_P, _P, _P, _IP, _FP, C.c_int32, C.c_float, C.c_int, _I64P]),
+    "slio_icp_correspond": (C.c_int, [_P, _FP, C.c_int, C.c_double, _DP, _I64P]),
+    "slio_icp_get_correspondences": (C.c_int, [_P, _IP, _FP]),
+    "slio_icp_get_working": (C.c_int, [_P, _FP, _FP, _FP, C.c_int64, _I64P]),
+    "slio_icp_far_queries": (C.c_int, [_P, _I64P]),
+    "slio_icp_params_default": (C.c_int, [C.POINTER(SlioIcpParams)]),
+    "slio_icp_state_init": (C.c_int, [C.POINTER(SlioIcpState), _FP]),
+    "slio_icp_step": (C.c_int, [_DP, C.c_int64, C.POINTER(SlioIcpParams), C.POINTER(SlioIcpState), _FP, _IP]),
     "slio_scan_upload_voxel": (C.c_int, [_P, _FP, _FP, _FP, C.c_int64, C.c_float, _I64P]),
     "slio_scan_download": (C.c_int, [_P, _FP, _FP, _FP]),
     "slio_map_add_points": (C.c_int, [_P, _FP, _FP, _FP, C.c_int64, C.c_int, C.c_float, _I64P]),

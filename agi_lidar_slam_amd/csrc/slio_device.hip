@@ -1371,8 +1371,10 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t& total) 
 // six slabs outside the ring's cube is per-axis exact (face distance on the
 // slab's axis, distance to the grid's range on the other two).  Keys carry
 // the fine pts position, so results equal the fine grid's.  Returns the list
-// in every lane.
-template <int U>
+// in every lane.  KNN = 1 (the loop-closure ICP pass, k_icp_pass) bounds and
+// ends the search by the nearest distance instead of the 5th: entry 0 is then
+// the exact nearest key, the same one a KNN = 5 search puts there.
+template <int U, int KNN = 5>
 __device__ __forceinline__ void far_search(const MapView& map, float qx, float qy, float qz,
                                         float bound, uint32_t* __restrict__ pre,
                                         uint32_t* __restrict__ beg, Top5& t) {
@@ -1523,8 +1525,8 @@ __device__ __forceinline__ void far_search(const MapView& map, float qx, float q
           }
         }
         group_merge<64>(t);  // every lane: the merged list
-        full = t.k[4] != kInfKey;
-        if (full) d5 = __uint_as_float((uint32_t)(t.k[4] >> 32));
+        full = t.k[KNN - 1] != kInfKey;
+        if (full) d5 = __uint_as_float((uint32_t)(t.k[KNN - 1] >> 32));
         if (lane != 0) top5_clear(t);  // lane 0 keeps it
         wave_fence();                  // pre / beg are rewritten by the next batch
       }
@@ -3786,7 +3788,14 @@ struct Ctx {
   std::vector<int64_t> kf_off, kf_len;
   MapDev::Buf kfb[3];         // map assembly: the concatenation (SoA), the segment table,
                               // build_index's input; kept across scans
-  IkfCtl* ctl = nullptr;    // device-resident update state (HBM)
+  hipEvent_t kf_ev = nullptr; // orders another handle's assembly after this store's pushes
+                              // (slio_s2m_loop_cloud)
+  // loop-closure ICP (slio_icp_correspond): the working cloud (SoA), the last
+  // pass's map id and squared distance per working point, the workgroup partials
+  MapDev::Buf icp[4];
+  int64_t icp_n = -1;         // working points (-1: no pass yet)
+  int64_t icp_far = 0;        // queries the last pass sent down the far path
+  IkfCtl* ctl = nullptr;   // device-resident update state (HBM)
   IkfCtl* h_ctl = nullptr;  // mapped, coherent host block: update input and output
   IkfCtl* d_hctl = nullptr; // its device view
   hipEvent_t done_ev = nullptr;  // end of a device-resident update (polled)
@@ -4546,6 +4555,9 @@ int slio_destroy(slio_handle h) {
     if (b.p) (void)hipFree(b.p);
   for (auto& b : h->c.kfb)
     if (b.p) (void)hipFree(b.p);
+  for (auto& b : h->c.icp)
+    if (b.p) (void)hipFree(b.p);
+  if (h->c.kf_ev) (void)hipEventDestroy(h->c.kf_ev);
   for (float* q : {h->c.kfx, h->c.kfy, h->c.kfz})
     if (q) (void)hipFree(q);
   if (h->c.comm) (void)ncclCommDestroy((ncclComm_t)h->c.comm);
@@ -5924,13 +5936,14 @@ k_vg_centroids4(const float* __restrict__ x, const float* __restrict__ y, const 
 // ---------------------------------------------------------------- keyframe map assembly
 // LIO-SAM extractCloud (mapOptmization.cpp:1204-1251): every selected
 // keyframe's cloud through transformPointCloud (:382-409) into one
-// concatenation, in ONE launch.  The keyframes live in the handle's SoA
-// arena; seg[s] describes the s-th NON-EMPTY selected entry: its first
-// position in the concatenation, its first position in the arena and the
+// concatenation, in ONE launch.  The keyframes live in the handles' SoA
+// arenas; seg[s] describes the s-th NON-EMPTY selected entry: its first
+// position in the concatenation, its first point in its arena and the
 // float affine of its pose (pcl::getTransformation, host).
 struct KfSeg {
-  int64_t start;  // arena position of the keyframe's first point
-  uint32_t off;   // concatenation position of the entry's first point
+  const float *x, *y, *z;  // the keyframe's first point in its store's arena (the loop-closure
+                           // cloud reads two stores in one launch: slio_s2m_loop_cloud)
+  uint32_t off;            // concatenation position of the entry's first point
   uint32_t pad;
   float m[12];
 };
@@ -5944,8 +5957,7 @@ constexpr int kKfTile = 256;
 // concatenation (k_vg_bbox's work) are folded in: one set of atomics per
 // workgroup.
 __global__ void __launch_bounds__(kKfTile)
-k_kf_gather(const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
-            const KfSeg* __restrict__ seg, int nseg, int64_t n, float* __restrict__ cx,
+k_kf_gather(const KfSeg* __restrict__ seg, int nseg, int64_t n, float* __restrict__ cx,
             float* __restrict__ cy, float* __restrict__ cz, int32_t* __restrict__ bb) {
   __shared__ KfSeg ls[kKfTile];
   int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
@@ -5981,8 +5993,8 @@ k_kf_gather(const float* __restrict__ ax, const float* __restrict__ ay, const fl
         if ((int64_t)ls[mid].off <= i) a = mid; else b = mid - 1;
       }
       const KfSeg& S = ls[a];
-      const int64_t j = S.start + (i - (int64_t)S.off);
-      const float x = ax[j], y = ay[j], z = az[j];
+      const int64_t j = i - (int64_t)S.off;
+      const float x = S.x[j], y = S.y[j], z = S.z[j];
       const float w[3] = {((S.m[0] * x + S.m[1] * y) + S.m[2] * z) + S.m[3],
                           ((S.m[4] * x + S.m[5] * y) + S.m[6] * z) + S.m[7],
                           ((S.m[8] * x + S.m[9] * y) + S.m[10] * z) + S.m[11]};
@@ -7786,6 +7798,252 @@ int slio_s2m_normal_equations(slio_handle h_corner, slio_handle h_surf, const fl
 
 }  // extern "C"
 
+// ---------------------------------------------------------------- LIO-SAM loop closure: one ICP pass
+// performLoopClosure's pcl::IterativeClosestPoint (mapOptmization.cpp:766-780)
+// as PCL 1.10 runs it (the reference tree carries no PCL source; slio.h
+// restates the rules): per iteration transformCloud of the working cloud,
+// CorrespondenceEstimation::determineCorrespondences (1-NN, distance gate)
+// and the sums TransformationEstimationSVD needs -- ONE launch.  The handle's
+// map is the target, its scan the source.  One query per lane on the 3x3x3
+// fine cells around it; a query whose nearest is not certified there
+// (outside_bound, as the search pass's block step) is deferred to the
+// workgroup's far queue and answered by a whole wavefront on the coarse level
+// (far_search<U, 1>).  A loop candidate starts metres from where it belongs:
+// in the first passes most queries take the far path.  Keys are those of the
+// search pass (float squared distance, then position in the cell-sorted
+// points), so the nearest point equals entry 0 of slio_get_neighbors for the
+// same world point, ties included.
+// The 16 sums (+ the count, + the far queries) are reduced as k_s2m_rows
+// reduces its rows: a butterfly over each wavefront, the four wavefronts in
+// order, one partial per workgroup.
+constexpr int kIcpSums = 18;  // p (3), q (3), q p^T (9), sqd, correspondences, far queries
+// (sx / sy / sz may be wx / wy / wz: no __restrict__ on the six)
+__global__ __launch_bounds__(256) void k_icp_pass(const MapView map, const float* sx, const float* sy,
+                                                  const float* sz, int64_t n, Aff12 T, double max_sq, float* wx,
+                                                  float* wy, float* wz, int32_t* __restrict__ idx,
+                                                  float* __restrict__ sqd, double* __restrict__ partial) {
+  __shared__ double red[4 * kIcpSums];
+  __shared__ int far_cnt;
+  __shared__ float4 far_q[256];
+  __shared__ uint8_t far_slot[256];
+  __shared__ uint64_t far_key[256];
+  __shared__ uint32_t far_pre[4][64], far_beg[4][64];
+  const int tid = threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+  const GridGeom g = map.g;
+  const float INF = __int_as_float(0x7f800000);
+  if (tid == 0) far_cnt = 0;
+  __syncthreads();
+  const bool live = i < n;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  if (live) {
+    // (in place when sx is wx: each lane reads its own point before it writes it)
+    const float x = sx[i], y = sy[i], z = sz[i];
+    qx = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+    qy = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+    qz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+    wx[i] = qx;
+    wy[i] = qy;
+    wz[i] = qz;
+  }
+  const bool finite = live && isfinite(qx) && isfinite(qy) && isfinite(qz) && map.n > 0;
+  uint64_t best = kInfKey;
+  bool done = !finite;
+  if (finite) {
+    const int cx = cell_coord(qx, g.ox, g.inv_h), cy = cell_coord(qy, g.oy, g.inv_h),
+              cz = cell_coord(qz, g.oz, g.inv_h);
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dx - 1);
+    if (x0 <= x1)
+      for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy) {
+          const int y = cy + dy, z = cz + dz;
+          if (y < 0 || y >= g.dy || z < 0 || z >= g.dz) continue;
+          const int64_t rb = ((int64_t)z * g.dy + y) * g.dx;
+          const uint32_t s = map.start[rb + x0], e = map.start[rb + x1 + 1];
+          for (uint32_t a = s; a < e; ++a) {
+            const float4 c = map.pts[a];
+            const float ddx = qx - c.x, ddy = qy - c.y, ddz = qz - c.z;
+            const float d = (ddx * ddx + ddy * ddy) + ddz * ddz;  // as consider()
+            const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint64_t)a;
+            best = key < best ? key : best;
+          }
+        }
+    bool covers;
+    const float b1 = outside_bound(g, cx, cy, cz, 1, qx, qy, qz, covers);
+    const float d1 = __uint_as_float((uint32_t)(best >> 32));
+    done = covers || (best != kInfKey && b1 > 0.0f && d1 < (b1 * b1) * 0.99999f);
+    if (!done) {
+      const int k = atomicAdd(&far_cnt, 1);
+      far_slot[k] = (uint8_t)tid;
+      far_q[k] = make_float4(qx, qy, qz, best != kInfKey ? d1 : INF);  // a real point's distance bounds the search
+    }
+  }
+  __syncthreads();
+  const int nfar = far_cnt;
+  for (int k = tid >> 6; k < nfar; k += 4) {  // (uniform per wavefront)
+    const float4 q = far_q[k];
+    Top5 tf;
+    far_search<4, 1>(map, q.x, q.y, q.z, q.w, far_pre[tid >> 6], far_beg[tid >> 6], tf);
+    if ((tid & 63) == 0) far_key[far_slot[k]] = tf.k[0];
+  }
+  __syncthreads();
+  const bool was_far = finite && !done;
+  if (was_far) best = far_key[tid];
+  double v[kIcpSums];
+#pragma unroll
+  for (int k = 0; k < kIcpSums; ++k) v[k] = 0.0;
+  if (live) {
+    int32_t id = -1;
+    float d = INF;
+    if (best != kInfKey) {
+      const float4 c = map.pts[(uint32_t)best];
+      d = __uint_as_float((uint32_t)(best >> 32));
+      // CorrespondenceEstimation: `if (distance > max_dist_sqr) continue;`
+      if ((double)d <= max_sq) {
+        id = (int32_t)__float_as_uint(c.w);
+        const float p[3] = {qx, qy, qz}, m[3] = {c.x, c.y, c.z};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          v[a] = (double)p[a];
+          v[3 + a] = (double)m[a];
+#pragma unroll
+          for (int b = 0; b < 3; ++b) v[6 + 3 * a + b] = (double)m[a] * (double)p[b];
+        }
+        v[15] = (double)d;
+        v[16] = 1.0;
+      }
+    }
+    idx[i] = id;
+    sqd[i] = d;
+  }
+  v[17] = was_far ? 1.0 : 0.0;
+  // (a + b == b + a: both lanes of a butterfly pair hold the same sum)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int k = 0; k < kIcpSums; ++k) v[k] = v[k] + __shfl_xor(v[k], off);
+  const int w = tid >> 6;
+  if ((tid & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < kIcpSums; ++k) red[w * kIcpSums + k] = v[k];
+  __syncthreads();
+  if (tid < kIcpSums)
+    partial[(int64_t)blockIdx.x * kIcpSums + tid] =
+        ((red[tid] + red[kIcpSums + tid]) + red[2 * kIcpSums + tid]) + red[3 * kIcpSums + tid];
+}
+
+extern "C" {
+
+int slio_icp_correspond(slio_handle h, const float T[16], int from_scan, double max_dist, double sums[16],
+                        int64_t* ncorr) {
+  if (!h) {
+    set_error("null handle");
+    return SLIO_EINVAL;
+  }
+  if (!T || !sums || !ncorr || (from_scan != 0 && from_scan != 1) || !(max_dist >= 0.0) ||
+      h->c.prm.nranks != 1) {
+    set_error("slio_icp_correspond: bad arguments");
+    return SLIO_EINVAL;
+  }
+  Ctx& c = h->c;
+  if (!c.map || (from_scan && !c.bx && c.n > 0) || (!from_scan && c.icp_n < 0)) {
+    set_error(from_scan || !c.map ? "slio_icp_correspond: map and scan needed"
+                                  : "slio_icp_correspond: no working cloud (from_scan = 1 first)");
+    return SLIO_ESTATE;
+  }
+  SLIO_HIP(hipSetDevice(c.prm.device));
+  const int64_t n = from_scan ? c.n : c.icp_n;
+  for (int k = 0; k < 16; ++k) sums[k] = 0.0;
+  *ncorr = 0;
+  c.icp_far = 0;
+  c.icp_n = n;
+  if (n == 0) return SLIO_OK;
+  const int nb = (int)((n + 255) / 256);
+  hipError_t e;
+  if ((e = MapDev::take(c.icp[0], 12 * n)) || (e = MapDev::take(c.icp[1], 4 * n)) ||
+      (e = MapDev::take(c.icp[2], 4 * n)) || (e = MapDev::take(c.icp[3], 8 * (size_t)kIcpSums * nb))) {
+    c.icp_n = -1;
+    set_error(std::string("slio_icp_correspond: hipMalloc: ") + hipGetErrorString(e));
+    return SLIO_ENOMEM;
+  }
+  float* wx = (float*)c.icp[0].p;
+  float* wy = wx + n;
+  float* wz = wx + 2 * n;
+  double* part = (double*)c.icp[3].p;
+  Aff12 A;
+  std::memcpy(A.m, T, sizeof(A.m));
+  if (int rc = map_refresh(c); rc) return rc;
+  {
+    std::shared_lock<std::shared_mutex> lk(c.map->mu);
+    if (int rc = map_read_sync(c)) return rc;
+    const CoarseView cv{c.map->cg, c.map->clo, c.map->chi};
+    const MapView mv{c.map->g,      c.map->n,    c.map->pts,    c.map->start, c.map->blk,
+                     c.map->bstart, c.map->nblk, c.map->ncells, cv};
+    k_icp_pass<<<nb, 256, 0, c.stream>>>(mv, from_scan ? c.bx : wx, from_scan ? c.by : wy, from_scan ? c.bz : wz, n,
+                                         A, max_dist * max_dist, wx, wy, wz, (int32_t*)c.icp[1].p,
+                                         (float*)c.icp[2].p, part);
+    SLIO_HIP(hipGetLastError());
+  }
+  std::vector<double> hp((size_t)nb * kIcpSums);
+  const Rb rb{hp.data(), part, 8 * hp.size()};
+  SLIO_HIP(readback(c.stream, &rb, 1));
+  double acc[kIcpSums] = {0};
+  for (int b = 0; b < nb; ++b)
+    for (int k = 0; k < kIcpSums; ++k) acc[k] = acc[k] + hp[(size_t)b * kIcpSums + k];
+  for (int k = 0; k < 16; ++k) sums[k] = acc[k];
+  *ncorr = (int64_t)llround(acc[16]);
+  c.icp_far = (int64_t)llround(acc[17]);
+  return SLIO_OK;
+}
+
+int slio_icp_get_correspondences(slio_handle h, int32_t* idx, float* sqd) {
+  SLIO_CHECK_H(h);
+  Ctx& c = h->c;
+  if (c.icp_n < 0) {
+    set_error("slio_icp_get_correspondences: no pass yet");
+    return SLIO_ESTATE;
+  }
+  if (c.icp_n > 0) {
+    SLIO_HIP(hipStreamSynchronize(c.stream));
+    if (idx) SLIO_HIP(hipMemcpy(idx, c.icp[1].p, 4 * c.icp_n, hipMemcpyDeviceToHost));
+    if (sqd) SLIO_HIP(hipMemcpy(sqd, c.icp[2].p, 4 * c.icp_n, hipMemcpyDeviceToHost));
+  }
+  return SLIO_OK;
+}
+
+int slio_icp_get_working(slio_handle h, float* x, float* y, float* z, int64_t cap, int64_t* n) {
+  SLIO_CHECK_H(h);
+  Ctx& c = h->c;
+  if (c.icp_n < 0) {
+    set_error("slio_icp_get_working: no pass yet");
+    return SLIO_ESTATE;
+  }
+  if (n) *n = c.icp_n;
+  if (cap < c.icp_n || (c.icp_n > 0 && (!x || !y || !z))) {
+    set_error("slio_icp_get_working: buffer too small");
+    return SLIO_ECAPACITY;
+  }
+  if (c.icp_n > 0) {
+    const float* w = (const float*)c.icp[0].p;
+    SLIO_HIP(hipStreamSynchronize(c.stream));
+    SLIO_HIP(hipMemcpy(x, w, 4 * c.icp_n, hipMemcpyDeviceToHost));
+    SLIO_HIP(hipMemcpy(y, w + c.icp_n, 4 * c.icp_n, hipMemcpyDeviceToHost));
+    SLIO_HIP(hipMemcpy(z, w + 2 * c.icp_n, 4 * c.icp_n, hipMemcpyDeviceToHost));
+  }
+  return SLIO_OK;
+}
+
+int slio_icp_far_queries(slio_handle h, int64_t* n) {
+  if (!h || !n) {
+    set_error(h ? "slio_icp_far_queries: bad arguments" : "null handle");
+    return SLIO_EINVAL;
+  }
+  *n = h->c.icp_far;
+  return SLIO_OK;
+}
+
+}  // extern "C"
+
 // ---------------------------------------------------------------- scan undistortion
 struct UndistEnd {
   double R[9], RL[9], TL[3], pos[3];
@@ -8250,40 +8508,83 @@ int slio_s2m_kf_get(slio_handle h, int32_t key, float* x, float* y, float* z, in
   return SLIO_OK;
 }
 
-int slio_s2m_map_from_keyframes(slio_handle h, const int32_t* key_ind, const float* poses6, int32_t nsel,
-                                float leaf, int64_t counts[2]) {
-  static const char* who = "slio_s2m_map_from_keyframes";
-  SLIO_KF_ARGS(nsel < 0 || (nsel > 0 && (!key_ind || !poses6)) || !(leaf > 0.0f), "slio_s2m_map_from_keyframes");
-  Ctx& c = h->c;
-  // the segment table: non-empty entries only, so a tile of the gather
-  // touches at most one segment per point
-  std::vector<KfSeg> seg;
-  int64_t n = 0;
+}  // extern "C"
+
+// The segment table of an assembly: for i in list order keyframe key_ind[i]
+// of every store in src[0..nsrc), at pose poses6[6 i ..]; non-empty entries
+// only, so a tile of the gather touches at most one segment per point.  No
+// device call.
+static int kf_segments(const Ctx* const* src, int nsrc, const int32_t* key_ind, const float* poses6, int32_t nsel,
+                       std::vector<KfSeg>& seg, int64_t& n, const char* who) {
+  n = 0;
   for (int32_t i = 0; i < nsel; ++i) {
     const int32_t k = key_ind[i];
-    if (k < 0 || (size_t)k >= c.kf_off.size()) {
+    if (k < 0 || (size_t)k >= src[0]->kf_off.size()) {
       set_error(std::string(who) + ": key index " + std::to_string(k) + " out of range");
       return SLIO_EINVAL;
     }
-    if (c.kf_len[k] == 0) continue;
-    // the (int)n radix sorts of the VoxelGrid and of build_index
-    if (n + c.kf_len[k] > (int64_t)INT32_MAX) {
-      set_error(std::string(who) + ": more than 2^31 - 1 points selected");
-      return SLIO_ECAPACITY;
-    }
-    KfSeg s;
-    s.start = c.kf_off[k];
-    s.off = (uint32_t)n;
-    s.pad = 0;
     const Aff12 T = s2m_affine(poses6 + 6 * (int64_t)i);
-    std::memcpy(s.m, T.m, sizeof(s.m));
-    seg.push_back(s);
-    n += c.kf_len[k];
+    for (int a = 0; a < nsrc; ++a) {
+      const Ctx& sc = *src[a];
+      if (sc.kf_len[k] == 0) continue;
+      // the (int)n radix sorts of the VoxelGrid and of build_index
+      if (n + sc.kf_len[k] > (int64_t)INT32_MAX) {
+        set_error(std::string(who) + ": more than 2^31 - 1 points selected");
+        return SLIO_ECAPACITY;
+      }
+      KfSeg s;
+      s.x = sc.kfx + sc.kf_off[k];
+      s.y = sc.kfy + sc.kf_off[k];
+      s.z = sc.kfz + sc.kf_off[k];
+      s.off = (uint32_t)n;
+      s.pad = 0;
+      std::memcpy(s.m, T.m, sizeof(s.m));
+      seg.push_back(s);
+      n += sc.kf_len[k];
+    }
   }
-  SLIO_HIP(hipSetDevice(c.prm.device));
+  return SLIO_OK;
+}
+
+// Gather-transform the n points of `seg` into one concatenation on c's
+// stream, VoxelGrid it with edge `leaf`, and make the result c's map
+// (slio_s2m_map_from_keyframes, slio_s2m_loop_cloud) or c's scan
+// (slio_s2m_loop_cloud, as_scan).
+static int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float leaf, bool as_scan,
+                       int64_t counts[2], const char* who) {
   hipStream_t st = c.stream;
-  int rc = nbr_settle_shared(c);  // the map it was searched on is replaced
+  int rc = nbr_settle_shared(c);  // the map (scan) it was searched on (with) is replaced
   if (rc) return rc;
+  if (as_scan) {
+    float *cx = nullptr, *cy = nullptr, *cz = nullptr;
+    if (n > 0) {
+      hipError_t e;
+      if ((e = MapDev::take(c.kfb[0], 12 * n)) || (e = MapDev::take(c.kfb[1], sizeof(KfSeg) * seg.size()))) {
+        set_error(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+        return SLIO_ENOMEM;
+      }
+      cx = (float*)c.kfb[0].p;
+      cy = cx + n;
+      cz = cx + 2 * n;
+      KfSeg* dseg = (KfSeg*)c.kfb[1].p;
+      VgWork w{};  // (the gather folds its box into w.bb; the scan's VoxelGrid makes its own)
+      if ((rc = vg_begin(c, n, who, w))) return rc;
+      SLIO_HIP(hipMemcpyAsync(dseg, seg.data(), sizeof(KfSeg) * seg.size(), hipMemcpyHostToDevice, st));
+      const int64_t ntiles = (n + kKfTile - 1) / kKfTile;
+      k_kf_gather<<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(dseg, (int)seg.size(), n, cx, cy, cz,
+                                                                           w.bb);
+      SLIO_HIP(hipGetLastError());
+    }
+    // downSizeFilterICP into the scan, as slio_scan_upload_voxel ends (one
+    // readback there: `seg` has left the host when it returns)
+    int64_t m = 0;
+    if ((rc = voxel_device(c, cx, cy, cz, n, leaf, &m))) return rc;
+    if (counts) {
+      counts[0] = n;
+      counts[1] = m;
+    }
+    return SLIO_OK;
+  }
   int64_t m = 0;
   float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
   float4* in4 = nullptr;
@@ -8304,8 +8605,8 @@ int slio_s2m_map_from_keyframes(slio_handle h, const int32_t* key_ind, const flo
     // (pageable source: the copy has left `seg` when the call returns)
     SLIO_HIP(hipMemcpyAsync(dseg, seg.data(), sizeof(KfSeg) * seg.size(), hipMemcpyHostToDevice, st));
     const int64_t ntiles = (n + kKfTile - 1) / kKfTile;
-    k_kf_gather<<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(c.kfx, c.kfy, c.kfz, dseg, (int)seg.size(),
-                                                                         n, cx, cy, cz, w.bb);
+    k_kf_gather<<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(dseg, (int)seg.size(), n, cx, cy, cz,
+                                                                         w.bb);
     if ((rc = vg_enqueue(c, w, cx, cy, cz, n, leaf, true, who))) return rc;
     // the centroids go out before the count is known (the output has room for
     // n); then the call's ONE readback: voxel count, flags, both boxes
@@ -8378,6 +8679,59 @@ int slio_s2m_map_from_keyframes(slio_handle h, const int32_t* key_ind, const flo
     counts[1] = m;
   }
   return SLIO_OK;
+}
+
+extern "C" {
+
+int slio_s2m_map_from_keyframes(slio_handle h, const int32_t* key_ind, const float* poses6, int32_t nsel,
+                                float leaf, int64_t counts[2]) {
+  static const char* who = "slio_s2m_map_from_keyframes";
+  SLIO_KF_ARGS(nsel < 0 || (nsel > 0 && (!key_ind || !poses6)) || !(leaf > 0.0f), "slio_s2m_map_from_keyframes");
+  Ctx& c = h->c;
+  std::vector<KfSeg> seg;
+  int64_t n = 0;
+  const Ctx* src[1] = {&c};
+  if (int rc = kf_segments(src, 1, key_ind, poses6, nsel, seg, n, who)) return rc;
+  SLIO_HIP(hipSetDevice(c.prm.device));
+  return kf_assemble(c, seg, n, leaf, false, counts, who);
+}
+
+int slio_s2m_loop_cloud(slio_handle h_dst, slio_handle h_corner, slio_handle h_surf, const int32_t* key_ind,
+                        const float* poses6, int32_t nsel, float leaf, int as_scan, int64_t counts[2]) {
+  static const char* who = "slio_s2m_loop_cloud";
+  if (!h_dst || !h_corner || !h_surf) {
+    set_error("null handle");
+    return SLIO_EINVAL;
+  }
+  if (nsel < 0 || (nsel > 0 && (!key_ind || !poses6)) || !(leaf > 0.0f) || (as_scan != 0 && as_scan != 1)) {
+    set_error("slio_s2m_loop_cloud: bad arguments");
+    return SLIO_EINVAL;
+  }
+  Ctx& c = h_dst->c;
+  Ctx* const srcs[2] = {&h_corner->c, &h_surf->c};
+  for (const Ctx* s : {(const Ctx*)&c, (const Ctx*)srcs[0], (const Ctx*)srcs[1]})
+    if (s->prm.nranks != 1 || s->prm.device != c.prm.device) {
+      set_error("slio_s2m_loop_cloud: single-rank handles on one device only");
+      return SLIO_EINVAL;
+    }
+  if (srcs[0]->kf_off.size() != srcs[1]->kf_off.size()) {
+    set_error("slio_s2m_loop_cloud: the corner and surf stores hold different numbers of keyframes");
+    return SLIO_EINVAL;
+  }
+  std::vector<KfSeg> seg;
+  int64_t n = 0;
+  const Ctx* src[2] = {srcs[0], srcs[1]};
+  if (int rc = kf_segments(src, 2, key_ind, poses6, nsel, seg, n, who)) return rc;
+  SLIO_HIP(hipSetDevice(c.prm.device));
+  // the stores' pushes (copies on their own streams) come before the gather
+  if (n > 0)
+    for (Ctx* s : srcs) {
+      if (s == &c || s->stream == c.stream || (s == srcs[1] && srcs[1] == srcs[0])) continue;
+      if (!s->kf_ev) SLIO_HIP(hipEventCreateWithFlags(&s->kf_ev, hipEventDisableTiming));
+      SLIO_HIP(hipEventRecord(s->kf_ev, s->stream));
+      SLIO_HIP(hipStreamWaitEvent(c.stream, s->kf_ev, 0));
+    }
+  return kf_assemble(c, seg, n, leaf, as_scan != 0, counts, who);
 }
 
 }  // extern "C"

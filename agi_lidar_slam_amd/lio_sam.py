@@ -13,10 +13,22 @@ extractCloud (:1204-1251) run there, and extractNearby's key selection
 (:1152-1193, a few hundred poses) is host numpy (extract_nearby).
 transformUpdate's IMU blending (:1742-1781) and the factor graph are out of
 scope (SURVEY.md §8f-4 names the scan-to-map core).
+
+Loop closure (performLoopClosure :725-826) runs on the same keyframe stores:
+detect_loop_closure_distance (:836-873, host numpy), loopFindNearKeyframes
+(:945-972) and pcl::IterativeClosestPoint (:766-780) on the device
+(slio_s2m_loop_cloud, slio_icp_correspond) with the rigid fit and PCL's
+convergence rules on the host (slio_icp_step).  detectLoopClosureExternal
+(:883-938, "not used yet" in the reference) and the GTSAM between-factor the
+result feeds (:800-822) stay out of scope: perform_loop_closure returns what
+the factor is made from.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+import time
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -103,6 +115,68 @@ def extract_nearby(key_poses3d, key_times, t_cur: float, radius: float = 50.0, d
     return np.array(out, np.int32)
 
 
+def detect_loop_closure_distance(key_poses3d, key_times, t_cur: float, loop_index_container,
+                                 radius: float = 15.0, time_diff: float = 30.0):
+    """detectLoopClosureDistance (:836-873): (loopKeyCur, loopKeyPre) or None.
+    Host numpy, float32 distances as PCL.
+
+    loopKeyCur is the newest key; None when it already is in
+    loop_index_container (:842-843).  The poses within `radius`
+    (historyKeyframeSearchRadius) of the newest one are taken in ascending
+    distance, ties to the lower index and the radius test `<` as in
+    extract_nearby; the first whose stamp differs from t_cur
+    (timeLaserInfoCur) by more than `time_diff`
+    (historyKeyframeSearchTimeDiff) is loopKeyPre (:856-864).  None when
+    nothing qualifies or the match is the newest key itself (:867)."""
+    f = np.float32
+    P = np.ascontiguousarray(np.asarray(key_poses3d, dtype=f).reshape(-1, 3))
+    T = np.asarray(key_times, dtype=np.float64).reshape(-1)
+    n = P.shape[0]
+    if n == 0:
+        return None
+    cur = n - 1
+    if cur in loop_index_container:
+        return None
+    d = P - P[-1]
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    near = np.nonzero(d2 < f(radius) * f(radius))[0]
+    near = near[np.argsort(d2[near], kind="stable")]
+    pre = -1
+    for i in near:
+        if abs(T[i] - t_cur) > time_diff:
+            pre = int(i)
+            break
+    if pre == -1 or pre == cur:
+        return None
+    return cur, pre
+
+
+def pose_affine(pose6) -> np.ndarray:
+    """pcl::getTransformation(x, y, z, roll, pitch, yaw) of pose6 = (roll,
+    pitch, yaw, x, y, z) as a float32 4x4 (pclPointToAffine3f :443-447), the
+    arithmetic of the device path's assembly: float products of correctly
+    rounded float sines and cosines."""
+    f = np.float32
+    roll, pitch, yaw, x, y, z = (f(v) for v in np.asarray(pose6, dtype=f).reshape(6))
+    A, B = f(math.cos(float(yaw))), f(math.sin(float(yaw)))
+    Cc, D = f(math.cos(float(pitch))), f(math.sin(float(pitch)))
+    E, F = f(math.cos(float(roll))), f(math.sin(float(roll)))
+    DE, DF = D * E, D * F
+    return np.array([[A * Cc, A * DF - B * E, B * F + A * DE, x],
+                     [B * Cc, A * E + B * DF, B * DE - A * F, y],
+                     [-D, Cc * F, Cc * E, z],
+                     [0, 0, 0, 1]], dtype=f)
+
+
+class LoopClosure(NamedTuple):
+    """What performLoopClosure (:796-825) makes its between-factor from."""
+    pair: tuple            # (loopKeyCur, loopKeyPre)
+    pose_from: np.ndarray  # tCorrect = icp result * pose(loopKeyCur): x, y, z, roll, pitch, yaw
+    pose_to: np.ndarray    # pose(loopKeyPre): x, y, z, roll, pitch, yaw
+    noise: float           # icp.getFitnessScore(), the factor's six variances
+    iterations: int
+
+
 def _handle(max_points: int, grid_cell: float, device: int = 0):
     lib = L.load()
     p = L.SlioParams()
@@ -127,16 +201,20 @@ class ScanToMap:
         self.lib = L.load()
         self.hc = _handle(max_points, grid_cell, device)
         self.hs = _handle(max_points, grid_cell, device)
+        self.hl = None   # loop closure: map = prevKeyframeCloud, scan = cureKeyframeCloud
+        self._handle_args = (max_points, grid_cell, device)
+        self.icp_far_first = 0
+        self.icp_pass_ms = []
         self.n_corner = self.n_surf = 0
         self.isDegenerate = C.c_int(0)
         self.matP = np.zeros(36, np.float32)
         self.iterations = 0
 
     def close(self):
-        for h in (self.hc, self.hs):
+        for h in (self.hc, self.hs, getattr(self, "hl", None)):
             if h:
                 self.lib.slio_destroy(h)
-        self.hc = self.hs = None
+        self.hc = self.hs = self.hl = None
 
     def __del__(self):
         try:
@@ -217,6 +295,106 @@ class ScanToMap:
     def clear_keyframes(self) -> None:
         for h in (self.hc, self.hs):
             L.check(self.lib.slio_s2m_kf_clear(h), "clear_keyframes")
+
+    def loop_handle(self):
+        """The third handle (created on first use, freed in close): its map is
+        the loop closure's target, its scan the source."""
+        if self.hl is None:
+            self.hl = _handle(*self._handle_args)
+        return self.hl
+
+    def loop_find_near_keyframes(self, key: int, search_num: int, poses6_all, as_scan: bool,
+                                 leaf: float = 0.4) -> int:
+        """loopFindNearKeyframes (:945-972): keyframes key - search_num ..
+        key + search_num clipped to the store, corner then surf of each at its
+        own pose poses6_all[k] (roll, pitch, yaw, x, y, z), through
+        downSizeFilterICP (mappingICPSize) -- on the device, into the loop
+        handle's scan (as_scan) or map.  Returns the cloud's size."""
+        nk = C.c_int32()
+        L.check(self.lib.slio_s2m_kf_info(self.hc, C.byref(nk), None), "loopFindNearKeyframes")
+        poses_all = np.asarray(poses6_all, dtype=np.float32).reshape(-1, 6)
+        n_keys = min(nk.value, poses_all.shape[0])
+        keys = np.array([k for k in range(key - search_num, key + search_num + 1) if 0 <= k < n_keys], np.int32)
+        poses = np.ascontiguousarray(poses_all[keys]) if keys.size else np.zeros((0, 6), np.float32)
+        cnt = np.zeros(2, np.int64)
+        L.check(self.lib.slio_s2m_loop_cloud(self.loop_handle(), self.hc, self.hs, L.iptr(keys), L.fptr(poses),
+                                             keys.shape[0], leaf, 1 if as_scan else 0, L.i64ptr(cnt)),
+                "loopFindNearKeyframes")
+        return int(cnt[1])
+
+    def icp_align(self, max_corr_dist: float, guess: Optional[np.ndarray] = None):
+        """icp.align (:766-778) then getFitnessScore (:780) on the loop handle
+        (map = target, scan = source): one slio_icp_correspond launch and one
+        host slio_icp_step per iteration.  Returns (converged, final_T 4x4
+        float32, fitness, iterations, convergence_state); icp_far_first keeps
+        the first pass's far-query count, icp_pass_ms the host wall clock of
+        every slio_icp_correspond call (scripts/bench_aux.py s2m_loop)."""
+        lib, h = self.lib, self.loop_handle()
+        prm, st = L.SlioIcpParams(), L.SlioIcpState()
+        L.check(lib.slio_icp_params_default(C.byref(prm)), "icp params")
+        g = None if guess is None else np.ascontiguousarray(np.asarray(guess, dtype=np.float32).reshape(16))
+        L.check(lib.slio_icp_state_init(C.byref(st), None if g is None else L.fptr(g)), "icp state")
+        T = np.array(st.final_T, dtype=np.float32)
+        sums, nc = np.zeros(16, np.float64), C.c_int64()
+        delta, done = np.zeros(16, np.float32), C.c_int(0)
+        from_scan = 1
+        self.icp_pass_ms = []
+        while True:
+            t0 = time.perf_counter()
+            L.check(lib.slio_icp_correspond(h, L.fptr(T), from_scan, float(max_corr_dist), L.dptr(sums),
+                                            C.byref(nc)), "icp correspond")
+            self.icp_pass_ms.append((time.perf_counter() - t0) * 1e3)
+            if from_scan:
+                far = C.c_int64()
+                L.check(lib.slio_icp_far_queries(h, C.byref(far)), "icp far queries")
+                self.icp_far_first = far.value
+            L.check(lib.slio_icp_step(L.dptr(sums), nc.value, C.byref(prm), C.byref(st), L.fptr(delta),
+                                      C.byref(done)), "icp step")
+            if done.value:
+                break
+            T, from_scan = delta, 0
+        final_T = np.array(st.final_T, dtype=np.float32).reshape(4, 4)
+        L.check(lib.slio_icp_correspond(h, L.fptr(np.ascontiguousarray(final_T.reshape(16))), 1, math.inf,
+                                        L.dptr(sums), C.byref(nc)), "icp fitness")
+        # (getFitnessScore: the mean squared distance; no point at all reads as DBL_MAX)
+        fitness = float(sums[15]) / nc.value if nc.value > 0 else float(np.finfo(np.float64).max)
+        return bool(st.converged), final_T, fitness, int(st.iterations), int(st.convergence_state)
+
+    def perform_loop_closure(self, key_poses6, key_times, t_cur: float, loop_index_container: dict,
+                             radius: float = 15.0, time_diff: float = 30.0, search_num: int = 25,
+                             fitness_score: float = 0.3, leaf: float = 0.4) -> Optional[LoopClosure]:
+        """performLoopClosure (:725-826) up to the factor.  key_poses6 (N, 6) =
+        cloudKeyPoses6D as (roll, pitch, yaw, x, y, z), key_times their stamps,
+        t_cur = timeLaserInfoCur; radius / time_diff / search_num /
+        fitness_score = historyKeyframeSearchRadius / SearchTimeDiff /
+        SearchNum / FitnessScore.  Returns None where the reference returns
+        early: no candidate, clouds below 300 / 1000 points (:756), ICP not
+        converged or its fitness above fitness_score (:781-783).  Otherwise
+        records the pair in loop_index_container (:825) and returns it with
+        the corrected pose, loopKeyPre's pose and the noise score."""
+        f = np.float32
+        poses = np.ascontiguousarray(np.asarray(key_poses6, dtype=f).reshape(-1, 6))
+        det = detect_loop_closure_distance(poses[:, 3:6], key_times, t_cur, loop_index_container, radius, time_diff)
+        if det is None:
+            return None
+        cur, pre = det
+        n_src = self.loop_find_near_keyframes(cur, 0, poses, True, leaf)
+        n_tgt = self.loop_find_near_keyframes(pre, search_num, poses, False, leaf)
+        if n_src < 300 or n_tgt < 1000:
+            return None
+        conv, T, fitness, iters, _ = self.icp_align(2.0 * radius)
+        if not conv or fitness > fitness_score:
+            return None
+        t = np.matmul(T, pose_affine(poses[cur]))  # correctionLidarFrame * tWrong (float)
+        # pcl::getTranslationAndEulerAngles
+        roll = f(math.atan2(float(t[2, 1]), float(t[2, 2])))
+        pitch = f(math.asin(float(-t[2, 0])))
+        yaw = f(math.atan2(float(t[1, 0]), float(t[0, 0])))
+        pose_from = np.array([t[0, 3], t[1, 3], t[2, 3], roll, pitch, yaw], f)
+        p = poses[pre]
+        pose_to = np.array([p[3], p[4], p[5], p[0], p[1], p[2]], f)
+        loop_index_container[cur] = pre
+        return LoopClosure((cur, pre), pose_from, pose_to, f(fitness).item(), iters)
 
     def corner_optimization(self, transform: np.ndarray, count: bool = True) -> int:
         """:1303-1432; count: return the selected points (a device -> host

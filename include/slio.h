@@ -502,6 +502,121 @@ int slio_s2m_kf_get(slio_handle h, int32_t key, float* x, float* y, float* z,
 int slio_s2m_map_from_keyframes(slio_handle h, const int32_t* key_ind, const float* poses6,
                                 int32_t nsel, float leaf, int64_t counts[2]);
 
+/* -- loop closure (performLoopClosure, :725-826) ------------------------------
+ * loopFindNearKeyframes (:945-972) and pcl::IterativeClosestPoint (:766-780)
+ * on the device.  PCL is not part of the reference tree: what follows restates
+ * PCL 1.10 (registration/impl/icp.hpp, correspondence_estimation.hpp,
+ * transformation_estimation_svd.hpp, default_convergence_criteria.hpp,
+ * common/impl/transforms.hpp) and IS the specification of these entries, as
+ * slio_scan_upload_voxel's comment is for VoxelGrid.  Three stated departures
+ * from PCL: (1) the rigid fit runs in double and is rounded to float once
+ * (PCL: float throughout); (2) inside a voxel of downSizeFilterICP the points
+ * are summed in ascending position of the concatenation (PCL: in the order
+ * its index sort leaves them); (3) among map points at exactly equal float
+ * distance the nearest is the one this project's search returns first (the
+ * lower position in the map's cell-sorted order: entry 0 of
+ * slio_get_neighbors), where FLANN's kd-tree order is not pinned by anything.
+ * Argument errors are reported before any device call. */
+/* loopFindNearKeyframes (:945-972): for i in list order keyframe key_ind[i]
+ * of h_corner's store, then the same key of h_surf's store (:959-960), both
+ * through transformPointCloud with poses6[6 i ..] -- the float arithmetic of
+ * slio_s2m_map_from_keyframes -- concatenated, then downSizeFilterICP
+ * (:966-969, mappingICPSize) with edge `leaf` under that entry's VoxelGrid
+ * semantics (non-finite points dropped, in-voxel sums in ascending
+ * concatenation position, a leaf too small passes the cloud through).
+ * as_scan == 0: the result becomes h_dst's MAP, indexed as slio_map_upload
+ * would (ids 0..n-1); as_scan == 1: it becomes h_dst's SCAN, the end state of
+ * slio_scan_upload_voxel (ECAPACITY beyond max_points).  counts = {points
+ * concatenated, points kept}.  No point travels to the host.  The three
+ * handles must be live, single-rank and on one device, the two stores of equal
+ * length (EINVAL); h_dst may be one of the stores' handles.  The assembly runs
+ * on h_dst's stream, ordered by an event after what the stores' streams have
+ * pending, and has read the arenas when the call returns.  The caller must not
+ * push keyframes to either store concurrently (the reference holds `mtx`
+ * around the same reads, :730-735). */
+int slio_s2m_loop_cloud(slio_handle h_dst, slio_handle h_corner, slio_handle h_surf,
+                        const int32_t* key_ind, const float* poses6, int32_t nsel, float leaf,
+                        int as_scan, int64_t counts[2]);
+/* One ICP iteration's device work (icp.hpp computeTransformation's loop body
+ * up to the fit), one launch and one readback.  h's map is the target
+ * (setInputTarget), its scan the source (setInputSource).  T: row-major 4x4,
+ * top three rows used.  from_scan == 1: working cloud = T * scan (the initial
+ * transformPointCloud with the guess; also getFitnessScore's).  from_scan ==
+ * 0: working cloud = T * working cloud, in place -- PCL transforms
+ * input_transformed by each iteration's increment, not the source by the
+ * accumulated matrix.  Per coordinate ((m0 x + m1 y) + m2 z) + m3 in float.
+ * Every working point gets its exact nearest map point: float squared
+ * distance (dx dx + dy dy) + dz dz and tie rule of the search pass, so for the
+ * same world point it equals entry 0 of slio_get_neighbors bit for bit, index
+ * included.  The pair is a correspondence when (double)sqd <= max_dist *
+ * max_dist (CorrespondenceEstimation: `distance > max_dist_sqr` skips;
+ * INFINITY keeps every finite point); a non-finite working point has none.
+ * Over the correspondences, 16 fp64 sums in an order fixed by the point index
+ * alone (per workgroup of 256 a butterfly over each wavefront, the four
+ * wavefronts in order; the workgroups' partials in order): sums[0..2] = sum
+ * of p (working point), [3..5] = sum of q (its map point), [6 + 3 r + c] = sum
+ * of q_r p_c, [15] = sum of sqd.  Every term is an exact double (a product of
+ * two floats), only the additions round.  *ncorr = correspondences.
+ * getFitnessScore() (:780) is slio_icp_correspond(h, final_T, 1, INFINITY)
+ * and sums[15] / ncorr.  EINVAL: null handle or pointers, from_scan not 0 / 1,
+ * max_dist negative or NaN, a multi-rank handle; ESTATE: no map, no scan, or
+ * from_scan == 0 before any from_scan == 1. */
+int slio_icp_correspond(slio_handle h, const float T[16], int from_scan, double max_dist,
+                        double sums[16], int64_t* ncorr);
+/* The last pass, for tests: per working point its correspondence's map id
+ * (-1: none, gated out included) and the float squared distance to its
+ * nearest map point (+inf: non-finite point or empty map). */
+int slio_icp_get_correspondences(slio_handle h, int32_t* idx, float* sqd);
+/* The working cloud, for tests; cap = the buffers' length, *n its size. */
+int slio_icp_get_working(slio_handle h, float* x, float* y, float* z, int64_t cap, int64_t* n);
+/* Working points of the last pass whose nearest the 3x3x3 fine cells around
+ * them did not certify (answered exactly on the map's coarse level). */
+int slio_icp_far_queries(slio_handle h, int64_t* n);
+/* DefaultConvergenceCriteria::ConvergenceState */
+enum {
+  SLIO_ICP_NOT_CONVERGED = 0,
+  SLIO_ICP_ITERATIONS = 1,
+  SLIO_ICP_TRANSFORM = 2,
+  SLIO_ICP_ABS_MSE = 3,
+  SLIO_ICP_REL_MSE = 4,
+  SLIO_ICP_NO_CORRESPONDENCES = 5
+};
+typedef struct slio_icp_params {
+  int32_t max_iterations;            /* 100  (:768) */
+  int32_t reserved;
+  double transformation_epsilon;     /* 1e-6 (:769) */
+  double euclidean_fitness_epsilon;  /* 1e-6 (:770) */
+} slio_icp_params;
+typedef struct slio_icp_state {
+  float final_T[16];  /* final_transformation_, row-major (identity or the guess at start) */
+  double prev_mse;    /* correspondences_prev_mse_ (DBL_MAX at start) */
+  int32_t iterations; /* nr_iterations_ */
+  int32_t similar;    /* iterations_similar_transforms_ (stays 0: its limit is 0) */
+  int32_t convergence_state;
+  int32_t converged;
+} slio_icp_state;
+int slio_icp_params_default(slio_icp_params* p);
+/* guess == NULL: identity */
+int slio_icp_state_init(slio_icp_state* s, const float guess[16]);
+/* One turn of computeTransformation's loop after the correspondences, host
+ * only.  (1) ncorr < 3 (min_number_correspondences_): NO_CORRESPONDENCES,
+ * converged = 0, *done = 1.  (2) delta = TransformationEstimationSVD, i.e.
+ * pcl::umeyama without scaling, in double from the sums: means sum p / n, sum
+ * q / n; Sigma = (sum q p^T) / n - mu_q mu_p^T; 3x3 SVD, S = diag(1, 1,
+ * sign(det U det V)), R = U S V^T, t = mu_q - R mu_p; rounded to float (PCL
+ * computes this in float on demeaned points: departure (1) above).  (3)
+ * final_T = delta * final_T as a float 4x4 product (terms added in index
+ * order), ++iterations.  (4) DefaultConvergenceCriteria::hasConverged, in
+ * this order: iterations >= max_iterations -> ITERATIONS; cos = 0.5 (trace
+ * R_delta - 1) >= 0.99999 and |t_delta|^2 <= transformation_epsilon (the
+ * epsilon is compared with the SQUARED translation, as PCL does) ->
+ * TRANSFORM; mse = sums[15] / ncorr: |mse - prev_mse| <
+ * euclidean_fitness_epsilon -> ABS_MSE; |mse - prev_mse| / prev_mse < 1e-5 ->
+ * REL_MSE; each converges at once (max_iterations_similar_transforms_ is 0).
+ * Otherwise prev_mse = mse, NOT_CONVERGED, *done = 0. */
+int slio_icp_step(const double sums[16], int64_t ncorr, const slio_icp_params* params,
+                  slio_icp_state* state, float delta[16], int* done);
+
 /* Manifold helpers exported for tests (esekfom.hpp:59-73, 236-258). */
 int slio_state_boxplus(const slio_state* x, const double dx[24], slio_state* out);
 int slio_state_boxminus(const slio_state* x1, const slio_state* x2, double dx[24]);

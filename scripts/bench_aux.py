@@ -10,6 +10,10 @@
   s2m_map   one LIO-SAM local-map assembly (extractCloud) of 50 keyframes from the
             device keyframe store, against the host path it replaces (only when
             named: it also runs the CPU oracle)
+  s2m_loop  one LIO-SAM loop closure (loopFindNearKeyframes twice + ICP + fitness)
+            on the device: 51 keyframes in the store, the source keyframe's pose
+            off by 1 m and 3 deg, against a host restatement (scipy cKDTree +
+            numpy) over the same clouds (only when named)
 One JSON line per measurement (host wall clock around synchronous calls)."""
 import ctypes as C
 import json
@@ -255,8 +259,126 @@ def s2m_map(n_kf=50, n_surf=20000, n_corner=1000, reps=200):
     s.close()
 
 
+def s2m_loop(n_kf=51, n_surf=20000, n_corner=1000, reps=5):
+    """performLoopClosure's device work: the store holds n_kf keyframes (as
+    s2m_map's) plus the newest one, a fresh draw at keyframe 25's place whose
+    stored pose is off by 1 m and 3 deg of yaw; the target is keyframes 0..50
+    (loopKeyPre 25, historyKeyframeSearchNum 25) and the source the newest
+    keyframe alone, both through downSizeFilterICP (0.4); ICP with
+    max_corr_dist 30 and the fitness pass.  The host figure restates the ICP
+    (not the assemblies) on the same two clouds: scipy cKDTree (built once,
+    one query per pass, all cores) + numpy sums + the numpy Umeyama of
+    tests/icp_model.py.  far_start: one more first pass with the source 12 m
+    off, where most queries take the far path."""
+    import icp_model as M
+    from scipy.spatial import cKDTree
+    from agi_lidar_slam_amd import _lib as L, synth
+    from agi_lidar_slam_amd.lio_sam import ScanToMap
+    pr = synth.make_s2m_problem()
+    rng = np.random.default_rng(11)
+    s = ScanToMap(max_points=60000)
+    lib = s.lib
+
+    def pose_of(k):
+        return np.array([0.002 * k, -0.003 * k, 0.02 * k, 0.5 * k, -0.1 * k, 0.01 * k], np.float64)
+
+    def keyframe(pose):
+        R = M.rot_zyx(*pose[:3])
+        out = []
+        for mp, n in ((pr["corner_map"], n_corner), (pr["surf_map"], n_surf)):
+            w = mp[rng.choice(mp.shape[0], n)] + rng.normal(0, 0.05, (n, 3))
+            out.append(((w - pose[3:]) @ R).astype(np.float32))
+        return out
+
+    poses = [pose_of(k) for k in range(n_kf)]
+    for k in range(n_kf):
+        s.push_keyframe(*keyframe(poses[k]))
+    s.push_keyframe(*keyframe(poses[n_kf // 2]))
+    wrong = poses[n_kf // 2].copy()
+    wrong[2] += np.deg2rad(3.0)
+    wrong[3:] += [0.8, -0.6, 0.0]
+    poses = np.array(poses + [wrong], np.float32)
+    cur, pre = n_kf, n_kf // 2
+
+    def assemble():
+        return (s.loop_find_near_keyframes(cur, 0, poses, True), s.loop_find_near_keyframes(pre, 25, poses, False))
+
+    def run():
+        t0 = time.perf_counter()
+        sizes = assemble()
+        t1 = time.perf_counter()
+        res = s.icp_align(30.0)
+        t2 = time.perf_counter()
+        return sizes, res, (t1 - t0) * 1e3, (t2 - t1) * 1e3, list(s.icp_pass_ms), s.icp_far_first
+
+    run()
+    rows = [run() for _ in range(reps)]
+    sizes, res = rows[-1][0], rows[-1][1]
+    med = lambda v: float(np.median(v))  # noqa: E731
+    # the two clouds, for the host restatement
+    n_src, n_tgt = sizes
+    xs = [np.zeros(n_src, np.float32) for _ in range(3)]
+    L.check(lib.slio_scan_download(s.hl, *(L.fptr(a) for a in xs)), "scan_download")
+    src = np.stack(xs, 1)
+    xt = [np.zeros(n_tgt, np.float32) for _ in range(3)]
+    ids = np.zeros(n_tgt, np.uint32)
+    got = C.c_int64()
+    L.check(lib.slio_map_download(s.hl, *(L.fptr(a) for a in xt), ids.ctypes.data_as(C.POINTER(C.c_uint32)), n_tgt,
+                                  C.byref(got)), "map_download")
+    tgt = np.stack(xt, 1)
+
+    def host_icp():
+        t0 = time.perf_counter()
+        tree = cKDTree(tgt.astype(np.float64))
+        t_build = (time.perf_counter() - t0) * 1e3
+        st = M.State()
+        work, pass_ms = src.copy(), []
+
+        def one_pass(w, max_dist):
+            d, j = tree.query(w.astype(np.float64), k=1, workers=-1)
+            ok = d <= max_dist
+            p, q = w[ok].astype(np.float64), tgt[j[ok]].astype(np.float64)
+            sums = np.concatenate([p.sum(0), q.sum(0), (q.T @ p).reshape(9), [(d[ok] * d[ok]).sum()]])
+            return sums, int(ok.sum())
+        while True:
+            t1 = time.perf_counter()
+            sums, n = one_pass(work, 30.0)
+            pass_ms.append((time.perf_counter() - t1) * 1e3)
+            delta, done = M.step(sums, n, st)
+            if done:
+                break
+            work = M.transform32(delta, work)
+        sums, n = one_pass(M.transform32(st.final_T, src), np.inf)
+        return dict(ms_total=(time.perf_counter() - t0) * 1e3, ms_tree_build=t_build, ms_per_pass=med(pass_ms),
+                    iterations=st.iterations, fitness=sums[15] / max(n, 1))
+    host_icp()
+    host = host_icp()
+    # a far start: the source 12 m off (the first pass only)
+    shift = np.eye(4, dtype=np.float32)
+    shift[:3, 3] = [12.0, -9.0, 0.0]
+    sums, nc, far = np.zeros(16), C.c_int64(), C.c_int64()
+    tf = []
+    for _ in range(reps + 1):
+        t0 = time.perf_counter()
+        L.check(lib.slio_icp_correspond(s.hl, L.fptr(shift.reshape(16)), 1, 30.0, L.dptr(sums), C.byref(nc)), "icp")
+        tf.append((time.perf_counter() - t0) * 1e3)
+    L.check(lib.slio_icp_far_queries(s.hl, C.byref(far)), "far")
+    print(json.dumps({
+        "bench": "lio_sam_s2m_loop_closure", "keyframes": n_kf, "surf_points_per_keyframe": n_surf,
+        "corner_points_per_keyframe": n_corner, "source_points": n_src, "target_points": n_tgt,
+        "ms_two_assemblies": med([r[2] for r in rows]), "ms_per_icp_pass": med(rows[-1][4]),
+        "iterations": res[3], "convergence_state": res[4], "converged": res[0], "fitness": res[2],
+        "ms_icp_incl_fitness": med([r[3] for r in rows]), "ms_total": med([r[2] + r[3] for r in rows]),
+        "far_share_first_pass": rows[-1][5] / max(n_src, 1),
+        "far_start": {"shift_m": 15.0, "far_share": far.value / max(n_src, 1), "ms_pass": med(tf[1:])},
+        "host_ckdtree_numpy": host}), flush=True)
+    s.close()
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "s2m_loop" in what:
+        s2m_loop()
     if "s2m_map" in what:
         s2m_map()
     if "mapping" in what:
