@@ -144,6 +144,31 @@ class SlioLegoCounts(C.Structure):
                 ("orientation", C.c_float * 3)]
 
 
+LEGO_ODOM_SURF, LEGO_ODOM_CORNER = 0, 1
+
+
+class SlioLegoOdomParams(C.Structure):
+    """slio_lego_odom_params (include/slio_frontend.h)."""
+    _fields_ = [("nearest_feature_sq_dist", C.c_float), ("max_iterations", C.c_int32),
+                ("search_period", C.c_int32), ("skip_frame_num", C.c_int32), ("scan_period", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+class SlioLegoOdomOut(C.Structure):
+    _fields_ = [("transform_cur", C.c_float * 6), ("transform_sum", C.c_float * 6), ("inited", C.c_int32),
+                ("iters", C.c_int32 * 2), ("rows", C.c_int32 * 2), ("degenerate", C.c_int32 * 2),
+                ("n_corner_last", C.c_int32), ("n_surf_last", C.c_int32), ("published", C.c_int32),
+                ("n_outlier_last", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SlioLegoOdomState(C.Structure):
+    _fields_ = [("transform_cur", C.c_float * 6), ("transform_sum", C.c_float * 6),
+                ("imu_last", C.c_float * 3), ("imu_shift_from_start", C.c_float * 3),
+                ("imu_velo_from_start", C.c_float * 3), ("mat_p", C.c_float * 9),
+                ("system_inited", C.c_int32), ("is_degenerate", C.c_int32), ("frame_count", C.c_int32),
+                ("n_corner_last", C.c_int32), ("n_surf_last", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_void_p)
 
 _P = C.c_void_p
@@ -295,6 +320,18 @@ SIGNATURES = {
     "slio_lego_get_clouds": (C.c_int, [_P, _FP, _FP, _FP, _FP]),
     "slio_lego_profile": (C.c_int, [_P, C.c_int]),
     "slio_lego_profile_read": (C.c_int, [_P, _DP, _I64P]),
+    # include/slio_frontend.h (LeGO-LOAM scan-to-scan odometry)
+    "slio_lego_odom_params_default": (C.c_int, [C.POINTER(SlioLegoOdomParams)]),
+    "slio_lego_odom_enable": (C.c_int, [_P, C.POINTER(SlioLegoOdomParams)]),
+    "slio_lego_odom_reset": (C.c_int, [_P]),
+    "slio_lego_odom_run_async": (C.c_int, [_P]),
+    "slio_lego_odom_run": (C.c_int, [_P, C.POINTER(SlioLegoOdomOut)]),
+    "slio_lego_odom_get_last": (C.c_int, [_P, _FP, _FP, _FP]),
+    "slio_lego_odom_set_clouds": (C.c_int, [_P, _FP, C.c_int32, _FP, C.c_int32, _FP, C.c_int32, _FP, C.c_int32]),
+    "slio_lego_odom_set_state": (C.c_int, [_P, C.POINTER(SlioLegoOdomState)]),
+    "slio_lego_odom_get_state": (C.c_int, [_P, C.POINTER(SlioLegoOdomState)]),
+    "slio_lego_odom_pass": (C.c_int, [_P, C.c_int, C.c_int, _FP, _IP, _FP, _U8P, _FP, _FP, _IP]),
+    "slio_lego_odom_step": (C.c_int, [C.c_int, _FP, _FP, C.c_int32, C.c_int, _FP, _IP, _FP, _IP]),
 }
 
 _lib = None

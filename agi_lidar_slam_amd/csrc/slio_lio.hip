@@ -47,6 +47,7 @@
 
 #include "slio_common.hpp"
 #include "slio_frontend.h"
+#include "slio_lego_odom.hpp"
 
 namespace slio {
 namespace lio {
@@ -3087,9 +3088,7 @@ struct LegoImuDev {
   int seg;  // entries on the ring from last_it to last; > 0: their times are non-decreasing
 };
 
-struct LegoImuOutDev {
-  float rpy_start[3], rpy_cur[3], velo_from_start[3], angular_from_start[3], ang_last[3];
-};
+// LegoImuOutDev: slio_lego_odom.hpp (the back half reads it on the device)
 
 // adjustDistortion's per-point orientation before the halfPassed switch
 __device__ __forceinline__ float ori_a(float so, float px, float pz, bool& passes) {
@@ -3624,12 +3623,21 @@ struct slio_lego {
   FeatCfg fc{};
   FeatWork fw{};
   bool ran = false;
+  bool odom_fresh = false;     // a sweep the odometry has not consumed yet
+  LegoOdom* odom = nullptr;    // slio_lego_odom_enable (slio_lego_odom.hip)
   bool prof = false;
   bool prof_scan = false;  // SLIO_LIO_PROFILE_SCAN: the events span the whole scan
   double prof_ms = 0.0;
   int64_t prof_n = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, pool;
 };
+
+void slio::lego::lego_odom_view(slio_lego* h, LegoOdomView* v) {
+  const int64_t R = h->g.N;
+  *v = LegoOdomView{h->prm.device, h->stream, R * kCornerPerRing, R * kFlatPerRing, h->cells,
+                    h->c_sharp, h->c_flat, &h->c_less_sharp, &h->c_less_flat, h->outlier, h->nseg,
+                    h->counts, h->io, &h->ran, &h->odom_fresh, &h->odom};
+}
 
 namespace {
 
@@ -3662,6 +3670,8 @@ void lego_free(slio_lego* h) {
   for (void* p : dev)
     if (p) (void)hipFree(p);
   feat_work_free(h->fw);
+  if (h->odom) lego_odom_free(h->odom);
+  h->odom = nullptr;
   if (h->own) (void)hipStreamDestroy(h->own);
 }
 
@@ -4056,6 +4066,7 @@ int slio_lego_run_async(slio_lego_handle h) {
                         h->start_ring, fo, h->c_sharp, h->c_less_sharp, h->c_flat, h->c_less_flat, h->counts);
   LIO_HIP(hipGetLastError());
   h->ran = true;
+  h->odom_fresh = true;
   return SLIO_OK;
 }
 

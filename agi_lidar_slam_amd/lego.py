@@ -1,12 +1,16 @@
 """Host side of the LeGO-LOAM front-end, mirroring
-ImageProjection (LeGO-LOAM/src/imageProjection.cpp) and the front half of
-FeatureAssociation (featureAssociation.cpp: adjustDistortion,
-calculateSmoothness, markOccludedPoints, extractFeatures).
+ImageProjection (LeGO-LOAM/src/imageProjection.cpp) and the whole of
+FeatureAssociation::runFeatureAssociation (featureAssociation.cpp): the front
+half (adjustDistortion, calculateSmoothness, markOccludedPoints,
+extractFeatures) and, after `enable_odometry`, the back half -- the
+scan-to-scan odometry that produces /laser_odom_to_init
+(checkSystemInitialization, updateInitialGuess, updateTransformation,
+integrateTransformation, publishOdometry, publishCloudsLast).
 
 The IMU ring buffer that adjustDistortion reads is host state filled message
 by message (imuHandler + AccumulateIMUShiftAndRotation, :430-588); `LegoImu`
 restates it.  The device side lives behind include/slio_frontend.h
-(slio_lego_*).
+(slio_lego_*, slio_lego_odom_*).
 """
 from __future__ import annotations
 
@@ -117,12 +121,29 @@ class LegoImu:
                             float(imu["yaw"][k]), imu["acc"][k], imu["gyro"][k])
 
 
+def odometry_step(kind: int, AtA, AtB, nsel: int, iter_count: int, transform_cur, is_degenerate: int, matP):
+    """slio_lego_odom_step: calculateTransformation{Surf,Corner} from
+    cv::solve on (featureAssociation.cpp:1649-1695 / :1764-1814), the same
+    code the device loop runs in-kernel.  transform_cur [6] and matP [9]
+    (contiguous float32 arrays) are updated in place.  Returns (rc,
+    keep_going, is_degenerate); rc 1 means fewer than 10 rows and no step."""
+    a = np.ascontiguousarray(AtA, np.float32)
+    b = np.ascontiguousarray(AtB, np.float32)
+    deg, keep = C.c_int(int(is_degenerate)), C.c_int(1)
+    rc = L.load().slio_lego_odom_step(kind, L.fptr(a), L.fptr(b), int(nsel), iter_count, L.fptr(transform_cur),
+                                      C.byref(deg), L.fptr(matP), C.byref(keep))
+    if rc < 0:
+        L.check(rc, "slio_lego_odom_step")
+    return rc, keep.value, deg.value
+
+
 class LegoFrontEnd:
-    """ImageProjection::cloudHandler + the front half of
-    FeatureAssociation::runFeatureAssociation (adjustDistortion ..
-    extractFeatures) as one device pipeline (slio_lego_run): the range image,
-    segmentation and cloud_info never leave HBM.  No CPU fallback: without
-    libslio.so the constructor raises."""
+    """ImageProjection::cloudHandler + FeatureAssociation::runFeatureAssociation
+    as one device pipeline: the front half (adjustDistortion ..
+    extractFeatures, slio_lego_run) and, once `enable_odometry` was called, the
+    scan-to-scan odometry (slio_lego_odom_run).  The range image,
+    segmentation, cloud_info and the feature clouds never leave HBM.  No CPU
+    fallback: without libslio.so the constructor raises."""
 
     def __init__(self, params: LegoParams | None = None, device: int = 0, max_points: int = 0):
         self.params = params or LegoParams()
@@ -131,6 +152,7 @@ class LegoFrontEnd:
         self._p = self.params.to_c(device, max_points)
         L.check(self.lib.slio_lego_create(C.byref(self.h), C.byref(self._p)), "slio_lego_create")
         self.counts = L.SlioLegoCounts()
+        self._n_outlier_last = 0   # the device's count of published outlier points (odometry)
 
     def close(self):
         if self.h:
@@ -180,6 +202,138 @@ class LegoFrontEnd:
             imu.pointer_last_iteration = f["imu_out"]["pointer_last_iteration"]
             imu.ang_last = np.asarray(f["imu_out"]["ang_last"], np.float32)
         return f
+
+    # -------------------------------------------------------------- odometry
+    def enable_odometry(self, nearest_feature_sq_dist: float = 25.0, max_iterations: int = 25,
+                        search_period: int = 5, skip_frame_num: int = 1):
+        """Allocate the back half's device state (slio_lego_odom_enable);
+        calling it again resets it."""
+        p = L.SlioLegoOdomParams()
+        L.check(self.lib.slio_lego_odom_params_default(C.byref(p)), "odom_params_default")
+        p.nearest_feature_sq_dist, p.max_iterations = nearest_feature_sq_dist, max_iterations
+        p.search_period, p.skip_frame_num = search_period, skip_frame_num
+        p.scan_period = self.params.scanPeriod
+        L.check(self.lib.slio_lego_odom_enable(self.h, C.byref(p)), "odom_enable")
+        self._n_outlier_last = 0
+
+    def reset_odometry(self):
+        L.check(self.lib.slio_lego_odom_reset(self.h), "odom_reset")
+        self._n_outlier_last = 0
+
+    @staticmethod
+    def _odom_dict(o: L.SlioLegoOdomOut) -> dict:
+        return dict(transform_cur=np.array(o.transform_cur, np.float32),
+                    transform_sum=np.array(o.transform_sum, np.float32), inited=o.inited,
+                    iters=list(o.iters), rows=list(o.rows), degenerate=list(o.degenerate),
+                    n_corner_last=o.n_corner_last, n_surf_last=o.n_surf_last, published=o.published,
+                    n_outlier_last=o.n_outlier_last)
+
+    def odometry_run(self) -> dict:
+        """The back half for the sweep last run (slio_lego_odom_run)."""
+        o = L.SlioLegoOdomOut()
+        L.check(self.lib.slio_lego_odom_run(self.h, C.byref(o)), "odom_run")
+        self._n_outlier_last = o.n_outlier_last
+        return self._odom_dict(o)
+
+    def runFeatureAssociation(self, x, y, z, imu: LegoImu | None = None, time_scan_cur: float = 0.0):
+        """cloudHandler followed by the odometry; returns the odometry result
+        (`features` holds what cloudHandler returns)."""
+        f = self.cloudHandler(x, y, z, imu, time_scan_cur)
+        out = self.odometry_run()
+        out["features"] = f
+        return out
+
+    def odometry_pose(self):
+        """publishOdometry (:2106-2128): (quaternion xyzw, position) of
+        /laser_odom_to_init from the last transformSum, on the host
+        (tf::createQuaternionMsgFromRollPitchYaw(ts[2], -ts[0], -ts[1]))."""
+        ts = self.odometry_state()["transform_sum"].astype(np.float64)
+        hr, hp, hy = ts[2] * 0.5, -ts[0] * 0.5, -ts[1] * 0.5
+        cy, sy, cp, sp, cr, sr = (math.cos(hy), math.sin(hy), math.cos(hp), math.sin(hp), math.cos(hr),
+                                  math.sin(hr))
+        qx, qy = sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy
+        qz, qw = cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy
+        return np.array([-qy, -qz, qx, qw]), ts[3:6].copy()
+
+    def last_clouds(self) -> dict:
+        """What publishCloudsLast publishes (slio_lego_odom_get_last)."""
+        st = self.odometry_state()
+        cl = np.empty((st["n_corner_last"], 4), np.float32)
+        sl = np.empty((st["n_surf_last"], 4), np.float32)
+        ol = np.empty((self._n_outlier_last, 4), np.float32)   # only enable / reset / a run change it
+        L.check(self.lib.slio_lego_odom_get_last(self.h, L.fptr(cl), L.fptr(sl), L.fptr(ol)), "odom_get_last")
+        return dict(laserCloudCornerLast=cl, laserCloudSurfLast=sl, outlierCloudLast=ol)
+
+    # lockstep / test entries
+    _STATE_VEC = ("transform_cur", "transform_sum", "imu_last", "imu_shift_from_start",
+                  "imu_velo_from_start", "mat_p")
+    _STATE_INT = ("system_inited", "is_degenerate", "frame_count", "n_corner_last", "n_surf_last")
+
+    def odometry_state(self) -> dict:
+        s = L.SlioLegoOdomState()
+        L.check(self.lib.slio_lego_odom_get_state(self.h, C.byref(s)), "odom_get_state")
+        d = {k: np.array(getattr(s, k), np.float32) for k in self._STATE_VEC}
+        d.update({k: getattr(s, k) for k in self._STATE_INT})
+        return d
+
+    def set_odometry_state(self, **kw):
+        """Overwrite the named members of the odometry state."""
+        s = L.SlioLegoOdomState()
+        L.check(self.lib.slio_lego_odom_get_state(self.h, C.byref(s)), "odom_get_state")
+        for k, v in kw.items():
+            if k in self._STATE_VEC:
+                a = np.asarray(v, np.float32)
+                setattr(s, k, (C.c_float * a.size)(*a))
+            elif k in self._STATE_INT:
+                setattr(s, k, int(v))
+            else:
+                raise KeyError(k)
+        L.check(self.lib.slio_lego_odom_set_state(self.h, C.byref(s)), "odom_set_state")
+
+    def odometry_set_clouds(self, sharp, flat, corner_last, surf_last) -> int:
+        """Inject the four clouds (xyzi); returns the C status (SLIO_EINVAL
+        for a last cloud whose ring order decreases)."""
+        a = [np.ascontiguousarray(v, np.float32).reshape(-1, 4) for v in (sharp, flat, corner_last, surf_last)]
+        args = []
+        for v in a:
+            args += [L.fptr(v), v.shape[0]]
+        return self.lib.slio_lego_odom_set_clouds(self.h, *args)
+
+    def odometry_pass(self, kind: int, iter_count: int, transform_cur, n: int) -> dict:
+        """One correspondence + normal-equations pass (slio_lego_odom_pass);
+        n is the kind's query count."""
+        tc = np.ascontiguousarray(transform_cur, np.float32)
+        ind = np.empty((3, n), np.int32)
+        coeff, sel = np.empty((n, 4), np.float32), np.empty(n, np.uint8)
+        AtA, AtB, nsel = np.empty(9, np.float32), np.empty(3, np.float32), C.c_int32()
+        L.check(self.lib.slio_lego_odom_pass(self.h, kind, iter_count, L.fptr(tc), L.iptr(ind), L.fptr(coeff),
+                                             L.u8ptr(sel), L.fptr(AtA), L.fptr(AtB), C.byref(nsel)), "odom_pass")
+        return dict(ind=ind, coeff=coeff, sel=sel, AtA=AtA, AtB=AtB, nsel=nsel.value)
+
+    def odometry_step(self, kind: int, AtA, AtB, nsel: int, iter_count: int, transform_cur, is_degenerate: int,
+                      matP):
+        """The host export of the in-kernel step; transform_cur and matP
+        (float32 arrays) are updated in place.  Returns (rc, keep_going,
+        is_degenerate); rc 1: fewer than 10 rows, no step."""
+        return odometry_step(kind, AtA, AtB, nsel, iter_count, transform_cur, is_degenerate, matP)
+
+    def odometry_lockstep(self, kind: int, n: int, transform_cur, is_degenerate: int, matP, max_iterations=25):
+        """One loop of updateTransformation on the host: a pass and a step per
+        iteration, with the loop's `continue` and `break`.  Returns
+        (iterations, rows, degenerate of iteration 0, is_degenerate)."""
+        iters = rows = deg0 = 0
+        for it in range(max_iterations):
+            p = self.odometry_pass(kind, it, transform_cur, n)
+            iters, rows = it + 1, p["nsel"]
+            rc, keep, is_degenerate = odometry_step(kind, p["AtA"], p["AtB"], p["nsel"], it, transform_cur,
+                                                    is_degenerate, matP)
+            if rc == 1:
+                continue
+            if it == 0:
+                deg0 = is_degenerate
+            if not keep:
+                break
+        return iters, rows, deg0, is_degenerate
 
     # --------------------------------------------------------------- outputs
     def image(self) -> dict:

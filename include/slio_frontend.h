@@ -199,6 +199,121 @@ int slio_lego_get_clouds(slio_lego_handle h, float* sharp, float* less_sharp, fl
 int slio_lego_profile(slio_lego_handle h, int enable);
 int slio_lego_profile_read(slio_lego_handle h, double* ms, int64_t* launches);
 
+/* ----------------------------------------------------------------------
+ * LeGO-LOAM scan-to-scan odometry: the back half of
+ * FeatureAssociation::runFeatureAssociation (featureAssociation.cpp
+ * :2232-2248), which produces /laser_odom_to_init.  The Gauss-Newton loop of
+ * updateTransformation runs in one launch, without a host round trip between
+ * iterations; per sweep the host reads one slio_lego_odom_out.
+ *
+ * Stated departures from the reference:
+ *  - the 1-NN (kdtree nearestKSearch, k = 1) is exact and ties go to the
+ *    lower index; FLANN's order among equal distances is unpinned;
+ *  - the forward neighbour scan is bounded by the CURRENT feature count
+ *    (j < cornerPointsSharpNum / surfPointsFlatNum, :1316 / :1448) as the
+ *    reference writes it, and additionally by the last cloud's size, where
+ *    the reference would read past the cloud's end;
+ *  - sin / cos / asin / atan2 / sqrt of a float are the double function
+ *    rounded to float;
+ *  - the searches always run on the new last clouds.  The reference re-seats
+ *    its kd-trees only when the swapped clouds hold MORE than 10 / 100 points
+ *    (:2169) while updateTransformation returns early only BELOW 10 / 100
+ *    (:2037), so at exactly 10 corner or 100 surf points it searches the
+ *    trees of the sweep before.
+ * The neighbour scans are evaluated in parallel, which relies on
+ * int(intensity) (the ring) not decreasing with the index in the last
+ * clouds; every cloud the handle produces itself has that order.
+ * When the IMU is absent adjustDistortion's outputs read as 0 (the handle
+ * does not keep an earlier sweep's imu*Start as the reference's members do).
+ * ---------------------------------------------------------------------- */
+#define SLIO_LEGO_ODOM_SURF 0   /* findCorrespondingSurfFeatures + calculateTransformationSurf     */
+#define SLIO_LEGO_ODOM_CORNER 1 /* findCorrespondingCornerFeatures + calculateTransformationCorner */
+
+typedef struct slio_lego_odom_params {
+  float nearest_feature_sq_dist; /* nearestFeatureSearchSqDist (utility.h:89, 25)          */
+  int32_t max_iterations;        /* the 25 of updateTransformation :2039 / :2053 (<= 64)   */
+  int32_t search_period;         /* the 5 of iterCount % 5 == 0 (:1303 / :1426)            */
+  int32_t skip_frame_num;        /* skipFrameNum (:30, 1)                                  */
+  float scan_period;             /* scanPeriod (utility.h:28, 0.1)                         */
+  int32_t reserved[3];
+} slio_lego_odom_params;
+
+typedef struct slio_lego_odom_out {
+  float transform_cur[6], transform_sum[6];
+  int32_t inited;          /* 0: this call was checkSystemInitialization (:1964-1997)      */
+  int32_t iters[2];        /* iterations executed (surf, corner); 0 on the early return    */
+  int32_t rows[2];         /* rows selected at the last executed iteration                 */
+  int32_t degenerate[2];   /* isDegenerate of each loop's iteration 0 (0 if no step there) */
+  int32_t n_corner_last, n_surf_last; /* after the swap                                    */
+  int32_t published;       /* the frameCount >= skipFrameNum + 1 gate (:2176)              */
+  int32_t n_outlier_last;  /* points of the outlier cloud last published                   */
+  int32_t reserved;
+} slio_lego_odom_out;
+
+/* Every member variable the back half carries between sweeps. */
+typedef struct slio_lego_odom_state {
+  float transform_cur[6], transform_sum[6];
+  float imu_last[3];            /* imuRollLast, imuPitchLast, imuYawLast                    */
+  float imu_shift_from_start[3]; /* stays 0: this reference never calls ShiftToStartIMU     */
+  float imu_velo_from_start[3];
+  float mat_p[9];
+  int32_t system_inited, is_degenerate, frame_count, n_corner_last, n_surf_last;
+  int32_t reserved[3];
+} slio_lego_odom_state;
+
+int slio_lego_odom_params_default(slio_lego_odom_params* p);
+/* Allocates the odometry state (the "last" clouds double-buffered against
+ * the less-sharp / less-flat clouds, transformCur / transformSum, the
+ * correspondence indices).  Without it the handle behaves as before. */
+int slio_lego_odom_enable(slio_lego_handle h, const slio_lego_odom_params* params);
+/* Back to the constructor's state (:318-354: systemInitedLM = false,
+ * transforms 0, frameCount = skipFrameNum, so that the first sweep after
+ * checkSystemInitialization publishes). */
+int slio_lego_odom_reset(slio_lego_handle h);
+/* runFeatureAssociation :2232-2248 for the sweep last run, enqueued on the
+ * stream: checkSystemInitialization on the first sweep; afterwards
+ * updateInitialGuess, updateTransformation, integrateTransformation and
+ * publishCloudsLast (TransformToEnd, the pointer swap, adjustOutlierCloud).
+ * SLIO_ESTATE without a sweep (or slio_lego_odom_set_clouds) since the last
+ * call.  After it the handle's less-sharp / less-flat buffers hold the
+ * previous "last" clouds, as the reference's swapped Ptrs do. */
+int slio_lego_odom_run_async(slio_lego_handle h);
+/* slio_lego_odom_run_async + wait + the result; out may be NULL. */
+int slio_lego_odom_run(slio_lego_handle h, slio_lego_odom_out* out);
+/* What publishCloudsLast publishes: laserCloudCornerLast [n_corner_last * 4],
+ * laserCloudSurfLast [n_surf_last * 4] (both current after every sweep) and
+ * the axis-permuted outlier cloud of the last publishing sweep
+ * [n_outlier_last * 4].  Any may be NULL. */
+int slio_lego_odom_get_last(slio_lego_handle h, float* corner_xyzi, float* surf_xyzi, float* outlier_xyzi);
+
+/* Lockstep / test entries: the same kernels and the same step code, one host
+ * wait per call. */
+/* Replaces cornerPointsSharp, surfPointsFlat and the two last clouds (xyzi)
+ * and sets systemInitedLM; the less clouds become empty.  SLIO_EINVAL for a
+ * last cloud whose int(intensity) decreases with the index. */
+int slio_lego_odom_set_clouds(slio_lego_handle h, const float* sharp, int32_t n_sharp, const float* flat,
+                              int32_t n_flat, const float* corner_last, int32_t n_corner_last,
+                              const float* surf_last, int32_t n_surf_last);
+int slio_lego_odom_set_state(slio_lego_handle h, const slio_lego_odom_state* s);
+int slio_lego_odom_get_state(slio_lego_handle h, slio_lego_odom_state* s);
+/* One findCorresponding{Surf,Corner}Features(iter_count) pass at
+ * transform_cur plus the Jacobian rows and normal equations of
+ * calculateTransformation{Surf,Corner} (:1593-1648 / :1726-1762).  n is the
+ * kind's query count.  ind[3n] = pointSearch*Ind1 / Ind2 / Ind3 per query
+ * (Ind3 = -1 for corners; refreshed when iter_count % search_period == 0,
+ * else the ones cached by the kind's last refreshing pass -- each kind keeps
+ * its own, -1 before the first), coeff[4n] = s * (a, b, c, d) (0 where not
+ * selected), sel[n], AtA[9] / AtB[3]: fp64 sums rounded to float, in the
+ * fixed order of DESIGN.md §3.12.  Any output may be NULL. */
+int slio_lego_odom_pass(slio_lego_handle h, int kind, int iter_count, const float transform_cur[6],
+                        int32_t* ind, float* coeff, uint8_t* sel, float AtA[9], float AtB[3], int32_t* nsel);
+/* Host export of the in-kernel step (:1649-1695 / :1764-1814).  Returns 1
+ * without a step when nsel < 10 (the loop's `continue`).  keep_going = the
+ * reference function's bool (0: converged, the loop breaks).  A singular AtA
+ * gives a zero step, which counts as converged (as slio_s2m_lm_step). */
+int slio_lego_odom_step(int kind, const float AtA[9], const float AtB[3], int32_t nsel, int iter_count,
+                        float transform_cur[6], int* is_degenerate, float matP[9], int* keep_going);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,9 @@
             on the device: 51 keyframes in the store, the source keyframe's pose
             off by 1 m and 3 deg, against a host restatement (scipy cKDTree +
             numpy) over the same clouds (only when named)
+  lego_odom LeGO-LOAM front-end + scan-to-scan odometry on a 16 x 1800 sequence:
+            sweeps per second, the odometry call alone, the lockstep loop and
+            the numpy restatement (only when named)
 One JSON line per measurement (host wall clock around synchronous calls)."""
 import ctypes as C
 import json
@@ -375,8 +378,72 @@ def s2m_loop(n_kf=51, n_surf=20000, n_corner=1000, reps=5):
     s.close()
 
 
+def lego_odom(sweeps=12, restate=True):
+    """LeGO-LOAM front-end + scan-to-scan odometry on a VLP-16 16 x 1800
+    sequence (the moving analytic room of tests/test_lego_odom_cpu.py): sweeps
+    per second of upload + front-end + odometry, the front-end and the
+    odometry call alone, the lockstep loop (one pass and one host step per
+    iteration) and the numpy restatement (tests/lego_odom_model.py) on one
+    sweep's clouds, with the iteration counts."""
+    import lego_odom_model as M
+    from test_lego_odom_cpu import moving_sweep
+    from agi_lidar_slam_amd.lego import LegoFrontEnd, LegoParams
+    med = lambda v: float(np.median(v))  # noqa: E731
+    scans = [moving_sweep(k, horizon=1800) for k in range(sweeps)]
+    fe = LegoFrontEnd(LegoParams())
+    fe.enable_odometry()
+    fe.set_imu(None)
+    t_all, t_fe, t_od, iters, rows = [], [], [], [], []
+    lock = model = None
+    for rep in range(2):                     # the first round warms up
+        fe.reset_odometry()
+        for k, sc in enumerate(scans):
+            t0 = time.perf_counter()
+            fe.upload(sc["x"], sc["y"], sc["z"])
+            fe.run()
+            t1 = time.perf_counter()
+            if rep == 1 and k == sweeps - 1:
+                # the last sweep once more on the host: lockstep, then the restatement
+                f, st = fe.features(), fe.odometry_state()
+                last = fe.last_clouds()
+                tc, P = st["transform_cur"].copy(), st["mat_p"].copy()
+                tl = time.perf_counter()
+                li = [fe.odometry_lockstep(kind, f[name].shape[0], tc, st["is_degenerate"], P)[0]
+                      for kind, name in ((0, "surfPointsFlat"), (1, "cornerPointsSharp"))]
+                lock = dict(ms=(time.perf_counter() - tl) * 1e3, iters=li)
+                if restate:
+                    m = M.OdomModel()
+                    m.inited, m.transformCur = True, st["transform_cur"].copy()
+                    m.corner_last, m.surf_last = last["laserCloudCornerLast"], last["laserCloudSurfLast"]
+                    tm = time.perf_counter()
+                    mo = m.update_transformation(f["cornerPointsSharp"], f["surfPointsFlat"])
+                    model = dict(ms=(time.perf_counter() - tm) * 1e3, iters=mo["iters"])
+                t1 = time.perf_counter()
+            o = fe.odometry_run()
+            t2 = time.perf_counter()
+            if rep == 1 and k > 0:
+                t_fe.append((t1 - t0) * 1e3)
+                t_od.append((t2 - t1) * 1e3)
+                t_all.append((t2 - t0) * 1e3)
+                iters.append(o["iters"])
+                rows.append(o["rows"])
+    c = fe.counts
+    print(json.dumps({
+        "bench": "lego_odom", "n_scan": 16, "horizon_scan": 1800, "sweeps": len(t_all),
+        "points_per_sweep": int(scans[0]["x"].size), "n_sharp": int(c.n_sharp), "n_flat": int(c.n_flat),
+        "n_corner_last": o["n_corner_last"], "n_surf_last": o["n_surf_last"],
+        "sweeps_per_s_frontend_plus_odometry": 1e3 / med(t_all[:-1]), "ms_upload_frontend": med(t_fe[:-1]),
+        "ms_odometry_call": med(t_od), "iterations_surf_corner": [int(np.median([i[0] for i in iters])),
+                                                                  int(np.median([i[1] for i in iters]))],
+        "rows_surf_corner": [int(np.median([r[0] for r in rows])), int(np.median([r[1] for r in rows]))],
+        "lockstep_loop": lock, "numpy_restatement_loop": model}), flush=True)
+    fe.close()
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "lego_odom" in what:
+        lego_odom()
     if "s2m_loop" in what:
         s2m_loop()
     if "s2m_map" in what:
