@@ -208,6 +208,25 @@ SLIO_COMM_ID_BYTES = 128
 SLIO_GROUP_RCCL = 1
 SLIO_GROUP_DEVICE = 2
 
+class SlioLegoLastView(C.Structure):
+    _fields_ = [("corner_xyzi", C.c_void_p), ("surf_xyzi", C.c_void_p), ("outlier_xyzi", C.c_void_p),
+                ("n_corner", C.c_int32), ("n_surf", C.c_int32), ("n_outlier", C.c_int32),
+                ("published", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SlioLmapParams(C.Structure):
+    _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("leaf_corner", C.c_float),
+                ("leaf_surf", C.c_float), ("leaf_outlier", C.c_float), ("pose_leaf", C.c_float),
+                ("search_radius", C.c_float), ("max_iterations", C.c_int32), ("mapping_interval", C.c_float),
+                ("scan_period", C.c_float), ("keyframe_distance", C.c_float), ("grid_cell", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+class SlioLmapFusion(C.Structure):
+    _fields_ = [("transform_sum", C.c_float * 6), ("transform_bef_mapped", C.c_float * 6),
+                ("transform_aft_mapped", C.c_float * 6), ("transform_mapped", C.c_float * 6)]
+
+
 SIGNATURES = {
     "slio_params_default": (C.c_int, [C.POINTER(SlioParams)]),
     "slio_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioParams)]),
@@ -332,6 +351,28 @@ SIGNATURES = {
     "slio_lego_odom_get_state": (C.c_int, [_P, C.POINTER(SlioLegoOdomState)]),
     "slio_lego_odom_pass": (C.c_int, [_P, C.c_int, C.c_int, _FP, _IP, _FP, _U8P, _FP, _FP, _IP]),
     "slio_lego_odom_step": (C.c_int, [C.c_int, _FP, _FP, C.c_int32, C.c_int, _FP, _IP, _FP, _IP]),
+    "slio_lego_odom_last_view": (C.c_int, [_P, C.POINTER(SlioLegoLastView)]),
+    # include/slio.h (LeGO-LOAM mapping)
+    "slio_lmap_params_default": (C.c_int, [C.POINTER(SlioLmapParams)]),
+    "slio_lmap_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioLmapParams)]),
+    "slio_lmap_destroy": (C.c_int, [_P]),
+    "slio_lmap_get_handle": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
+    "slio_lmap_feed_lego": (C.c_int, [_P, _P, _I64P]),
+    "slio_lmap_feed_host": (C.c_int, [_P, _FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64, _I64P]),
+    "slio_lmap_extract": (C.c_int, [_P, _IP, C.c_int32, _I64P]),
+    "slio_lmap_coeffs": (C.c_int, [_P, C.c_int, _FP, _I64P]),
+    "slio_lmap_get_coeffs": (C.c_int, [_P, C.c_int, _FP, _U8P]),
+    "slio_lmap_normal_equations": (C.c_int, [_P, _FP, _FP, _I64P]),
+    "slio_lmap_optimize": (C.c_int, [_P, _FP, _IP, _IP]),
+    "slio_lmap_save_keyframe": (C.c_int, [_P, _FP, _IP]),
+    "slio_lmap_get_key_poses": (C.c_int, [_P, _FP, C.c_int32, _IP]),
+    "slio_lmap_clear": (C.c_int, [_P]),
+    "slio_lmap_associate_to_map": (C.c_int, [_FP, _FP, _FP, _FP]),
+    "slio_lmap_transform_update": (C.c_int, [_FP, _FP, C.c_double, C.c_float, _DP, _FP, _FP, C.c_int32, C.c_int32,
+                                             _IP, _FP, _FP]),
+    "slio_lmap_fuse": (C.c_int, [C.POINTER(SlioLmapFusion), _FP, _FP, _FP]),
+    "slio_lmap_keyframe_decision": (C.c_int, [_FP, _FP, C.c_int32, C.c_double, _IP]),
+    "slio_lmap_qr_solve": (C.c_int, [C.c_int, C.c_int, _FP, _FP, _FP]),
 }
 
 _lib = None

@@ -17,7 +17,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libslio.so")
 
 SOURCES = ["slio_device.hip", "slio_ikf.cpp", "slio_imu.cpp", "slio_s2m.cpp", "slio_lio.hip",
-           "slio_lego_odom.hip"]
+           "slio_lego_odom.hip", "slio_lmap.cpp"]
 HEADERS = ["slio_common.hpp", "slio_plane.hpp", "slio_so3.hpp", "slio_cvsolve.hpp", "slio_lego_odom.hpp"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

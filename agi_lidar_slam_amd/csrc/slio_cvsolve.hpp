@@ -3,7 +3,9 @@
 // float and templated on the size: 6 for LIO-SAM's LMOptimization
 // (slio_s2m.cpp), 3 for LeGO-LOAM's two-stage scan-to-scan step, which is
 // written here once for the host entry (slio_lego_odom_step) and for the
-// device loop (slio_lego_odom.hip).  OpenCV is third-party and absent.
+// device loop (slio_lego_odom.hip); 5 x 3 for the plane fit of LeGO-LOAM's
+// mapping (slio_device.hip, k_lmap_coeff).  OpenCV is third-party and absent:
+// what is written here is the specification of these solvers.
 #pragma once
 
 #include <cfloat>
@@ -132,37 +134,45 @@ SLIO_HD inline void jacobi(float* A, float* W, float* V) {
   }
 }
 
-// A x = b (N x N, float) by Householder QR.  false where OpenCV's QRImpl gives
-// up (cv::solve DECOMP_QR -> hal::QR32f with eps = 10 * FLT_EPSILON: a
-// diagonal entry of R below eps in magnitude)
-template <int N>
-SLIO_HD inline bool qr_solve(const float* A_in, const float* b_in, float* x) {
-  float A[N * N], b[N];
-  for (int i = 0; i < N * N; ++i) A[i] = A_in[i];
-  for (int i = 0; i < N; ++i) b[i] = b_in[i];
+// A x = b (M x N, M >= N, float, A row-major) by Householder QR, in the least
+// squares sense when M > N: cv::solve(A, b, x, cv::DECOMP_QR).  OpenCV is
+// third-party and absent here, so THIS RESTATEMENT IS THE SPECIFICATION of
+// the solve: one Householder reflection per column k over rows k..M-1, applied
+// to the remaining columns and to b, then back-substitution on the top N rows
+// of R.  false where OpenCV's QRImpl gives up (hal::QR32f with eps =
+// 10 * FLT_EPSILON: a diagonal entry of R below eps in magnitude); the caller
+// zeroes x then, as cv::solve leaves matX.  M == N is LIO-SAM's 6 x 6 and
+// LeGO-LOAM's 3 x 3 step; M = 5, N = 3 is the plane fit of LeGO-LOAM's
+// surfOptimization (mapOptmization.cpp:1395).
+template <int M, int N>
+SLIO_HD inline bool qr_solve_mn(const float* A_in, const float* b_in, float* x) {
+  static_assert(M >= N, "qr_solve_mn: M >= N");
+  float A[M * N], b[M];
+  for (int i = 0; i < M * N; ++i) A[i] = A_in[i];
+  for (int i = 0; i < M; ++i) b[i] = b_in[i];
   for (int k = 0; k < N; ++k) {
     float nrm = 0;
-    for (int i = k; i < N; ++i) nrm += A[N * i + k] * A[N * i + k];
+    for (int i = k; i < M; ++i) nrm += A[N * i + k] * A[N * i + k];
     nrm = sqrtf(nrm);
     if (nrm == 0) return false;
     const float alpha = A[N * k + k] > 0 ? -nrm : nrm;
-    float v[N];
-    for (int i = 0; i < N; ++i) v[i] = 0;
-    for (int i = k; i < N; ++i) v[i] = A[N * i + k];
+    float v[M];
+    for (int i = 0; i < M; ++i) v[i] = 0;
+    for (int i = k; i < M; ++i) v[i] = A[N * i + k];
     v[k] -= alpha;
     float vv = 0;
-    for (int i = k; i < N; ++i) vv += v[i] * v[i];
+    for (int i = k; i < M; ++i) vv += v[i] * v[i];
     if (vv == 0) continue;
     for (int j = k; j < N; ++j) {
       float d = 0;
-      for (int i = k; i < N; ++i) d += v[i] * A[N * i + j];
+      for (int i = k; i < M; ++i) d += v[i] * A[N * i + j];
       const float f = 2 * d / vv;
-      for (int i = k; i < N; ++i) A[N * i + j] -= f * v[i];
+      for (int i = k; i < M; ++i) A[N * i + j] -= f * v[i];
     }
     float d = 0;
-    for (int i = k; i < N; ++i) d += v[i] * b[i];
+    for (int i = k; i < M; ++i) d += v[i] * b[i];
     const float f = 2 * d / vv;
-    for (int i = k; i < N; ++i) b[i] -= f * v[i];
+    for (int i = k; i < M; ++i) b[i] -= f * v[i];
   }
   for (int i = N - 1; i >= 0; --i) {
     float s = b[i];
@@ -171,6 +181,12 @@ SLIO_HD inline bool qr_solve(const float* A_in, const float* b_in, float* x) {
     x[i] = s / A[N * i + i];
   }
   return true;
+}
+
+// the square case
+template <int N>
+SLIO_HD inline bool qr_solve(const float* A_in, const float* b_in, float* x) {
+  return qr_solve_mn<N, N>(A_in, b_in, x);
 }
 
 // inverse by LU with partial pivoting (cv::Mat::inv, DECOMP_LU, N > 3)

@@ -35,6 +35,8 @@
 #include <vector>
 
 #include "slio_common.hpp"
+#include "slio_cvsolve.hpp"
+#include "slio_frontend.h"
 #include "slio_plane.hpp"
 #include "slio_so3.hpp"
 
@@ -5949,13 +5951,36 @@ struct KfSeg {
 };
 constexpr int kKfTile = 256;
 
+// LeGO-LOAM's pointAssociateToMap / transformPointCloud
+// (LeGO-LOAM/src/mapOptmization.cpp:578-607, :624-652): not an affine but
+// three successive float rotations -- yaw about z, roll about x, pitch about
+// y -- then the translation, with the six cached float sines and cosines
+// (:562-576, :609-622; the trig in double, rounded to float, on the host)
+struct LegoRot {
+  float cr, sr, cp, sp, cy, sy, tx, ty, tz;
+};
+__device__ __forceinline__ void lego_to_map(const LegoRot& T, float x, float y, float z, float& ox, float& oy,
+                                            float& oz) {
+  const float x1 = T.cy * x - T.sy * y;
+  const float y1 = T.sy * x + T.cy * y;
+  const float z1 = z;
+  const float x2 = x1;
+  const float y2 = T.cr * y1 - T.sr * z1;
+  const float z2 = T.sr * y1 + T.cr * z1;
+  ox = T.cp * x2 + T.sp * z2 + T.tx;
+  oy = y2 + T.ty;
+  oz = -T.sp * x2 + T.cp * z2 + T.tz;
+}
+
 // Each workgroup takes tiles of kKfTile consecutive concatenation positions;
 // the segments a tile touches (at most kKfTile: none is empty) are staged in
 // LDS and each thread finds its own by bisection there.  World point =
 // m0 x + m1 y + m2 z + m3, left to right (:400-405; the build has
 // -ffp-contract=off).  The VoxelGrid box and finite count of the
 // concatenation (k_vg_bbox's work) are folded in: one set of atomics per
-// workgroup.
+// workgroup.  FORM 0: the affine above (LIO-SAM); FORM 1: m[0..8] is a
+// LegoRot and the point goes through lego_to_map (LeGO-LOAM).
+template <int FORM>
 __global__ void __launch_bounds__(kKfTile)
 k_kf_gather(const KfSeg* __restrict__ seg, int nseg, int64_t n, float* __restrict__ cx,
             float* __restrict__ cy, float* __restrict__ cz, int32_t* __restrict__ bb) {
@@ -5995,9 +6020,15 @@ k_kf_gather(const KfSeg* __restrict__ seg, int nseg, int64_t n, float* __restric
       const KfSeg& S = ls[a];
       const int64_t j = i - (int64_t)S.off;
       const float x = S.x[j], y = S.y[j], z = S.z[j];
-      const float w[3] = {((S.m[0] * x + S.m[1] * y) + S.m[2] * z) + S.m[3],
-                          ((S.m[4] * x + S.m[5] * y) + S.m[6] * z) + S.m[7],
-                          ((S.m[8] * x + S.m[9] * y) + S.m[10] * z) + S.m[11]};
+      float w[3];
+      if (FORM == 0) {
+        w[0] = ((S.m[0] * x + S.m[1] * y) + S.m[2] * z) + S.m[3];
+        w[1] = ((S.m[4] * x + S.m[5] * y) + S.m[6] * z) + S.m[7];
+        w[2] = ((S.m[8] * x + S.m[9] * y) + S.m[10] * z) + S.m[11];
+      } else {
+        const LegoRot R{S.m[0], S.m[1], S.m[2], S.m[3], S.m[4], S.m[5], S.m[6], S.m[7], S.m[8]};
+        lego_to_map(R, x, y, z, w[0], w[1], w[2]);
+      }
       cx[i] = w[0];
       cy[i] = w[1];
       cz[i] = w[2];
@@ -7515,6 +7546,83 @@ __device__ __forceinline__ void cv_jacobi3(float A[9], float W[3], float V[9]) {
   }
 }
 
+// cornerOptimization's point-to-line coefficient from the five neighbours
+// (LIO-SAM :1332-1425; LeGO-LOAM's :1237-1365 is the same arithmetic)
+__device__ __forceinline__ uint8_t s2m_corner_coeff(const float (&nb)[5][3], float x0, float y0, float z0,
+                                                    float4& cf) {
+  uint8_t ok = 0;
+  float cx = 0, cy = 0, cz = 0;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    cx += nb[j][0];
+    cy += nb[j][1];
+    cz += nb[j][2];
+  }
+  cx /= 5;
+  cy /= 5;
+  cz /= 5;
+  float a11 = 0, a12 = 0, a13 = 0, a22 = 0, a23 = 0, a33 = 0;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const float ax = nb[j][0] - cx, ay = nb[j][1] - cy, az = nb[j][2] - cz;
+    a11 += ax * ax;
+    a12 += ax * ay;
+    a13 += ax * az;
+    a22 += ay * ay;
+    a23 += ay * az;
+    a33 += az * az;
+  }
+  a11 /= 5;
+  a12 /= 5;
+  a13 /= 5;
+  a22 /= 5;
+  a23 /= 5;
+  a33 /= 5;
+  float A[9] = {a11, a12, a13, a12, a22, a23, a13, a23, a33}, W[3], V[9];
+  cv_jacobi3(A, W, V);
+  if (W[0] > 3 * W[1]) {
+    const float x1 = cx + 0.1 * V[0], y1 = cy + 0.1 * V[1], z1 = cz + 0.1 * V[2];
+    const float x2 = cx - 0.1 * V[0], y2 = cy - 0.1 * V[1], z2 = cz - 0.1 * V[2];
+    const float u = (x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1);
+    const float v = (x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1);
+    const float w = (y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1);
+    const float a012 = sqrtf(u * u + v * v + w * w);
+    const float l12 = sqrtf((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2));
+    const float la = ((y1 - y2) * u + (z1 - z2) * v) / a012 / l12;
+    const float lb = -((x1 - x2) * u - (z1 - z2) * w) / a012 / l12;
+    const float lc = -((x1 - x2) * v + (y1 - y2) * w) / a012 / l12;
+    const float ld2 = a012 / l12;
+    const float s = 1 - 0.9 * fabsf(ld2);
+    cf = make_float4(s * la, s * lb, s * lc, s * ld2);
+    ok = s > 0.1;
+  }
+  return ok;
+}
+
+// surfOptimization after the plane solve (LIO-SAM :1470-1508, LeGO-LOAM
+// :1403-1447): sol = the solve's x for b = -1
+__device__ __forceinline__ uint8_t s2m_surf_coeff(const float (&sol)[3], const float (&nb)[5][3], float x0, float y0,
+                                                  float z0, float4& cf) {
+  uint8_t ok = 0;
+  float pa = sol[0], pb = sol[1], pc = sol[2], pd = 1;
+  const float ps = sqrtf(pa * pa + pb * pb + pc * pc);
+  pa /= ps;
+  pb /= ps;
+  pc /= ps;
+  pd /= ps;
+  bool valid = true;
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+    if (fabsf(pa * nb[j][0] + pb * nb[j][1] + pc * nb[j][2] + pd) > 0.2) valid = false;
+  if (valid) {
+    const float pd2 = pa * x0 + pb * y0 + pc * z0 + pd;
+    const float s = 1 - 0.9 * fabsf(pd2) / sqrtf(sqrtf(x0 * x0 + y0 * y0 + z0 * z0));
+    cf = make_float4(s * pa, s * pb, s * pc, s * pd2);
+    ok = s > 0.1;
+  }
+  return ok;
+}
+
 // coefficients (coeff.x, y, z, intensity) and selection of every scan point
 template <int KIND>  // 0: corner (point-to-line), 1: surf (point-to-plane)
 __global__ void k_s2m_coeff(const float* __restrict__ wx, const float* __restrict__ wy,
@@ -7536,70 +7644,11 @@ __global__ void k_s2m_coeff(const float* __restrict__ wx, const float* __restric
       nb[j][2] = p.z;
     }
     if (KIND == 0) {
-      float cx = 0, cy = 0, cz = 0;
-#pragma unroll
-      for (int j = 0; j < 5; ++j) {
-        cx += nb[j][0];
-        cy += nb[j][1];
-        cz += nb[j][2];
-      }
-      cx /= 5;
-      cy /= 5;
-      cz /= 5;
-      float a11 = 0, a12 = 0, a13 = 0, a22 = 0, a23 = 0, a33 = 0;
-#pragma unroll
-      for (int j = 0; j < 5; ++j) {
-        const float ax = nb[j][0] - cx, ay = nb[j][1] - cy, az = nb[j][2] - cz;
-        a11 += ax * ax;
-        a12 += ax * ay;
-        a13 += ax * az;
-        a22 += ay * ay;
-        a23 += ay * az;
-        a33 += az * az;
-      }
-      a11 /= 5;
-      a12 /= 5;
-      a13 /= 5;
-      a22 /= 5;
-      a23 /= 5;
-      a33 /= 5;
-      float A[9] = {a11, a12, a13, a12, a22, a23, a13, a23, a33}, W[3], V[9];
-      cv_jacobi3(A, W, V);
-      if (W[0] > 3 * W[1]) {
-        const float x1 = cx + 0.1 * V[0], y1 = cy + 0.1 * V[1], z1 = cz + 0.1 * V[2];
-        const float x2 = cx - 0.1 * V[0], y2 = cy - 0.1 * V[1], z2 = cz - 0.1 * V[2];
-        const float u = (x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1);
-        const float v = (x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1);
-        const float w = (y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1);
-        const float a012 = sqrtf(u * u + v * v + w * w);
-        const float l12 = sqrtf((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2));
-        const float la = ((y1 - y2) * u + (z1 - z2) * v) / a012 / l12;
-        const float lb = -((x1 - x2) * u - (z1 - z2) * w) / a012 / l12;
-        const float lc = -((x1 - x2) * v + (y1 - y2) * w) / a012 / l12;
-        const float ld2 = a012 / l12;
-        const float s = 1 - 0.9 * fabsf(ld2);
-        cf = make_float4(s * la, s * lb, s * lc, s * ld2);
-        ok = s > 0.1;
-      }
+      ok = s2m_corner_coeff(nb, x0, y0, z0, cf);
     } else {
       float sol[3];
       qr_solve_m1_dev(nb, sol);
-      float pa = sol[0], pb = sol[1], pc = sol[2], pd = 1;
-      const float ps = sqrtf(pa * pa + pb * pb + pc * pc);
-      pa /= ps;
-      pb /= ps;
-      pc /= ps;
-      pd /= ps;
-      bool valid = true;
-#pragma unroll
-      for (int j = 0; j < 5; ++j)
-        if (fabsf(pa * nb[j][0] + pb * nb[j][1] + pc * nb[j][2] + pd) > 0.2) valid = false;
-      if (valid) {
-        const float pd2 = pa * x0 + pb * y0 + pc * z0 + pd;
-        const float s = 1 - 0.9 * fabsf(pd2) / sqrtf(sqrtf(x0 * x0 + y0 * y0 + z0 * z0));
-        cf = make_float4(s * pa, s * pb, s * pc, s * pd2);
-        ok = s > 0.1;
-      }
+      ok = s2m_surf_coeff(sol, nb, x0, y0, z0, cf);
     }
   }
   coeff[i] = cf;
@@ -7665,6 +7714,119 @@ __global__ __launch_bounds__(256) void k_s2m_rows(const float* __restrict__ bx, 
     partial[(int64_t)blockIdx.x * kS2mSums + k] =
         ((red[k] + red[kS2mSums + k]) + red[2 * kS2mSums + k]) + red[3 * kS2mSums + k];
   }
+}
+
+// ---- LeGO-LOAM mapping (LeGO-LOAM/src/mapOptmization.cpp) -------------------
+// pointAssociateToMap (:578-607) of the scan: see lego_to_map
+__global__ void k_lmap_transform(const float* __restrict__ bx, const float* __restrict__ by,
+                                 const float* __restrict__ bz, int64_t n, LegoRot T, float* __restrict__ wx,
+                                 float* __restrict__ wy, float* __restrict__ wz) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  lego_to_map(T, bx[i], by[i], bz[i], wx[i], wy[i], wz[i]);
+}
+
+// cornerOptimization (:1222-1370) / surfOptimization (:1372-1450) after the
+// search, and LMOptimization's rows (:1477-1537) of the same points, in ONE
+// launch: a row needs only the body point and the coefficient its thread has
+// just computed.  The corner arithmetic is LIO-SAM's (s2m_corner_coeff); the
+// plane comes from cv::solve(DECOMP_QR) on the 5 x 3 system (:1395,
+// cvs::qr_solve_mn<5, 3>), a failed solve leaving x = 0 as cv::solve does: ps
+// is then 0, everything NaN, and `s > 0.1` is false.  The rows use pointOri and
+// coeff as they are (LeGO-LOAM works in its camera-like frame throughout: no
+// axis swap) and are summed exactly as k_s2m_rows sums them.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_lmap_coeff(
+    const float* __restrict__ bx, const float* __restrict__ by, const float* __restrict__ bz,
+    const float* __restrict__ wx, const float* __restrict__ wy, const float* __restrict__ wz, int64_t n,
+    const uint32_t* __restrict__ nbr_pos, const float* __restrict__ nbr_sqd, const float4* __restrict__ pts,
+    float4* __restrict__ coeff, uint8_t* __restrict__ sel, S2mTrig T, double* __restrict__ partial) {
+  __shared__ double red[4 * kS2mSums];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double v[kS2mSums];
+#pragma unroll
+  for (int k = 0; k < kS2mSums; ++k) v[k] = 0.0;
+  if (i < n) {
+    uint8_t ok = 0;
+    float4 cf = make_float4(0, 0, 0, 0);
+    const float x0 = wx[i], y0 = wy[i], z0 = wz[i];
+    if (nbr_sqd[i * 5 + 4] < 1.0f) {  // (false for +inf: fewer than 5 map points)
+      float nb[5][3];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        const float4 p = pts[nbr_pos[i * 5 + j]];
+        nb[j][0] = p.x;
+        nb[j][1] = p.y;
+        nb[j][2] = p.z;
+      }
+      if (KIND == 0) {
+        ok = s2m_corner_coeff(nb, x0, y0, z0, cf);
+      } else {
+        const float m1[5] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f};
+        float sol[3];
+        if (!slio::cvs::qr_solve_mn<5, 3>(&nb[0][0], m1, sol)) sol[0] = sol[1] = sol[2] = 0.0f;
+        ok = s2m_surf_coeff(sol, nb, x0, y0, z0, cf);
+      }
+    }
+    coeff[i] = cf;
+    sel[i] = ok;
+    if (ok) {
+      const float px = bx[i], py = by[i], pz = bz[i];
+      const float cx = cf.x, cy = cf.y, cz = cf.z;
+      const float srx = T.srx, crx = T.crx, sry = T.sry, cry = T.cry, srz = T.srz, crz = T.crz;
+      const float arx = (crx * sry * srz * px + crx * crz * sry * py - srx * sry * pz) * cx +
+                        (-srx * srz * px - crz * srx * py - crx * pz) * cy +
+                        (crx * cry * srz * px + crx * cry * crz * py - cry * srx * pz) * cz;
+      const float ary = ((cry * srx * srz - crz * sry) * px + (sry * srz + cry * crz * srx) * py + crx * cry * pz) * cx +
+                        ((-cry * crz - srx * sry * srz) * px + (cry * srz - crz * srx * sry) * py - crx * sry * pz) * cz;
+      const float arz = ((crz * srx * sry - cry * srz) * px + (-cry * crz - srx * sry * srz) * py) * cx +
+                        (crx * crz * px - crx * srz * py) * cy +
+                        ((sry * srz + cry * crz * srx) * px + (crz * sry - cry * srx * srz) * py) * cz;
+      const float a[6] = {arx, ary, arz, cx, cy, cz};
+      const float b = -cf.w;
+      int q = 0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) v[q++] = (double)a[r] * (double)a[c];
+#pragma unroll
+      for (int r = 0; r < 6; ++r) v[21 + r] = (double)a[r] * (double)b;
+      v[27] = 1.0;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int k = 0; k < kS2mSums; ++k) v[k] = v[k] + __shfl_xor(v[k], off);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < kS2mSums; ++k) red[w * kS2mSums + k] = v[k];
+  __syncthreads();
+  if (threadIdx.x < kS2mSums) {
+    const int k = threadIdx.x;
+    partial[(int64_t)blockIdx.x * kS2mSums + k] =
+        ((red[k] + red[kS2mSums + k]) + red[2 * kS2mSums + k]) + red[3 * kS2mSums + k];
+  }
+}
+
+// float4 xyzi (the front-end's clouds) -> SoA, for the VoxelGrid
+__global__ void k_lmap_split4(const float4* __restrict__ in, int64_t n, float* __restrict__ x,
+                              float* __restrict__ y, float* __restrict__ z) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = in[i];
+  x[i] = p.x;
+  y[i] = p.y;
+  z[i] = p.z;
+}
+
+// the six cached float sines and cosines (:562-576 / :609-622) of
+// {rx, ry, rz, tx, ty, tz}: roll = rx, pitch = ry, yaw = rz
+static LegoRot lmap_rot(const float tf[6]) {
+  auto fc = [](float a) { return (float)std::cos((double)a); };
+  auto fs = [](float a) { return (float)std::sin((double)a); };
+  return LegoRot{fc(tf[0]), fs(tf[0]), fc(tf[1]), fs(tf[1]), fc(tf[2]), fs(tf[2]), tf[3], tf[4], tf[5]};
 }
 
 // pcl::getTransformation (pcl/common/impl/eigen.hpp) in float, the trig
@@ -8514,8 +8676,10 @@ int slio_s2m_kf_get(slio_handle h, int32_t key, float* x, float* y, float* z, in
 // of every store in src[0..nsrc), at pose poses6[6 i ..]; non-empty entries
 // only, so a tile of the gather touches at most one segment per point.  No
 // device call.
+// form 0: poses6 = {roll, pitch, yaw, x, y, z} as a float affine (LIO-SAM);
+// form 1: poses6 = LeGO-LOAM's {rx, ry, rz, tx, ty, tz} as a LegoRot
 static int kf_segments(const Ctx* const* src, int nsrc, const int32_t* key_ind, const float* poses6, int32_t nsel,
-                       std::vector<KfSeg>& seg, int64_t& n, const char* who) {
+                       std::vector<KfSeg>& seg, int64_t& n, const char* who, int form = 0) {
   n = 0;
   for (int32_t i = 0; i < nsel; ++i) {
     const int32_t k = key_ind[i];
@@ -8523,7 +8687,13 @@ static int kf_segments(const Ctx* const* src, int nsrc, const int32_t* key_ind, 
       set_error(std::string(who) + ": key index " + std::to_string(k) + " out of range");
       return SLIO_EINVAL;
     }
-    const Aff12 T = s2m_affine(poses6 + 6 * (int64_t)i);
+    Aff12 T{};
+    if (form == 0) {
+      T = s2m_affine(poses6 + 6 * (int64_t)i);
+    } else {
+      const LegoRot R = lmap_rot(poses6 + 6 * (int64_t)i);
+      std::memcpy(T.m, &R, sizeof(R));
+    }
     for (int a = 0; a < nsrc; ++a) {
       const Ctx& sc = *src[a];
       if (sc.kf_len[k] == 0) continue;
@@ -8551,7 +8721,7 @@ static int kf_segments(const Ctx* const* src, int nsrc, const int32_t* key_ind, 
 // (slio_s2m_map_from_keyframes, slio_s2m_loop_cloud) or c's scan
 // (slio_s2m_loop_cloud, as_scan).
 static int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float leaf, bool as_scan,
-                       int64_t counts[2], const char* who) {
+                       int64_t counts[2], const char* who, int form = 0) {
   hipStream_t st = c.stream;
   int rc = nbr_settle_shared(c);  // the map (scan) it was searched on (with) is replaced
   if (rc) return rc;
@@ -8571,8 +8741,12 @@ static int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float l
       if ((rc = vg_begin(c, n, who, w))) return rc;
       SLIO_HIP(hipMemcpyAsync(dseg, seg.data(), sizeof(KfSeg) * seg.size(), hipMemcpyHostToDevice, st));
       const int64_t ntiles = (n + kKfTile - 1) / kKfTile;
-      k_kf_gather<<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(dseg, (int)seg.size(), n, cx, cy, cz,
-                                                                           w.bb);
+      if (form == 0)
+        k_kf_gather<0><<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(dseg, (int)seg.size(), n, cx, cy,
+                                                                                cz, w.bb);
+      else
+        k_kf_gather<1><<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(dseg, (int)seg.size(), n, cx, cy,
+                                                                                cz, w.bb);
       SLIO_HIP(hipGetLastError());
     }
     // downSizeFilterICP into the scan, as slio_scan_upload_voxel ends (one
@@ -8605,8 +8779,12 @@ static int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float l
     // (pageable source: the copy has left `seg` when the call returns)
     SLIO_HIP(hipMemcpyAsync(dseg, seg.data(), sizeof(KfSeg) * seg.size(), hipMemcpyHostToDevice, st));
     const int64_t ntiles = (n + kKfTile - 1) / kKfTile;
-    k_kf_gather<<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(dseg, (int)seg.size(), n, cx, cy, cz,
-                                                                         w.bb);
+    if (form == 0)
+      k_kf_gather<0><<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(dseg, (int)seg.size(), n, cx, cy, cz,
+                                                                              w.bb);
+    else
+      k_kf_gather<1><<<(int)std::min<int64_t>(ntiles, 1024), kKfTile, 0, st>>>(dseg, (int)seg.size(), n, cx, cy, cz,
+                                                                              w.bb);
     if ((rc = vg_enqueue(c, w, cx, cy, cz, n, leaf, true, who))) return rc;
     // the centroids go out before the count is known (the output has room for
     // n); then the call's ONE readback: voxel count, flags, both boxes
@@ -8732,6 +8910,453 @@ int slio_s2m_loop_cloud(slio_handle h_dst, slio_handle h_corner, slio_handle h_s
       SLIO_HIP(hipStreamWaitEvent(c.stream, s->kf_ev, 0));
     }
   return kf_assemble(c, seg, n, leaf, as_scan != 0, counts, who);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- LeGO-LOAM mapping
+// mapOptmization.cpp of LeGO-LOAM with loopClosureEnableFlag = false
+// (slio_lmap_*, slio.h): downsampleCurrentScan from the front-end's device
+// clouds, extractSurroundingKeyFrames' map assembly from three keyframe
+// stores, cornerOptimization / surfOptimization / LMOptimization's rows
+// (k_lmap_coeff) and scan2MapOptimization's loop.  The mapper owns four
+// handles that share one stream, so every stage is ordered by the stream
+// alone.  The host formulas (transformAssociateToMap, transformUpdate,
+// transformFusion, the keyframe decision) are in slio_lmap.cpp.
+struct slio_lmap {
+  slio_lmap_params prm{};
+  slio_handle h[4] = {nullptr, nullptr, nullptr, nullptr};
+  std::vector<float> poses6;   // cloudKeyPoses6D: {rx, ry, rz, tx, ty, tz} per key
+  bool coeff_ok[2] = {false, false};
+};
+
+static int lmap_check(slio_lmap_handle m, const char* who) {
+  if (!m) {
+    set_error(std::string(who) + ": null mapper");
+    return SLIO_EINVAL;
+  }
+  return SLIO_OK;
+}
+
+// VoxelGrid of n device points (float4 xyzi) into handle c's scan
+static int lmap_voxel4(Ctx& c, const float4* src, int64_t n, float leaf, int64_t* n_down) {
+  float *dx_ = nullptr, *dy_ = nullptr, *dz_ = nullptr;
+  if (n > 0) {
+    hipError_t e;
+    if ((e = MapDev::take(c.pre[0], 12 * n))) {
+      set_error(std::string("slio_lmap_feed: hipMalloc: ") + hipGetErrorString(e));
+      return SLIO_ENOMEM;
+    }
+    dx_ = (float*)c.pre[0].p;
+    dy_ = dx_ + n;
+    dz_ = dx_ + 2 * n;
+    k_lmap_split4<<<grid_blocks(n), 256, 0, c.stream>>>(src, n, dx_, dy_, dz_);
+    SLIO_HIP(hipGetLastError());
+  }
+  return voxel_device(c, dx_, dy_, dz_, n, leaf, n_down);
+}
+
+// downsampleCurrentScan (:1197-1220) from three device clouds
+static int lmap_feed_dev(slio_lmap* m, const float4* corner, int64_t nc, const float4* surf, int64_t ns,
+                         const float4* outlier, int64_t no, int64_t counts[4]) {
+  m->coeff_ok[0] = m->coeff_ok[1] = false;
+  int64_t k[4] = {0, 0, 0, 0};
+  Ctx& cc = m->h[SLIO_LMAP_CORNER]->c;
+  Ctx& ct = m->h[SLIO_LMAP_SURF_TOTAL]->c;
+  Ctx& cs = m->h[SLIO_LMAP_SURF]->c;
+  Ctx& co = m->h[SLIO_LMAP_OUTLIER]->c;
+  if (int rc = lmap_voxel4(cc, corner, nc, m->prm.leaf_corner, &k[0])) return rc;
+  if (int rc = lmap_voxel4(cs, surf, ns, m->prm.leaf_surf, &k[2])) return rc;
+  if (int rc = lmap_voxel4(co, outlier, no, m->prm.leaf_outlier, &k[3])) return rc;
+  // laserCloudSurfTotalLast = surfLastDS ++ outlierLastDS (:1215-1216), then
+  // downSizeFilterSurf again (:1217-1218)
+  const int64_t nt = k[2] + k[3];
+  float *tx = nullptr, *ty = nullptr, *tz = nullptr;
+  if (nt > 0) {
+    hipError_t e;
+    if ((e = MapDev::take(ct.pre[0], 12 * nt))) {
+      set_error(std::string("slio_lmap_feed: hipMalloc: ") + hipGetErrorString(e));
+      return SLIO_ENOMEM;
+    }
+    tx = (float*)ct.pre[0].p;
+    ty = tx + nt;
+    tz = tx + 2 * nt;
+    const Ctx* src[2] = {&cs, &co};
+    int64_t o = 0;
+    for (const Ctx* s : src) {
+      if (s->n == 0) continue;
+      SLIO_HIP(hipMemcpyAsync(tx + o, s->bx, 4 * s->n, hipMemcpyDeviceToDevice, ct.stream));
+      SLIO_HIP(hipMemcpyAsync(ty + o, s->by, 4 * s->n, hipMemcpyDeviceToDevice, ct.stream));
+      SLIO_HIP(hipMemcpyAsync(tz + o, s->bz, 4 * s->n, hipMemcpyDeviceToDevice, ct.stream));
+      o += s->n;
+    }
+  }
+  if (int rc = voxel_device(ct, tx, ty, tz, nt, m->prm.leaf_surf, &k[1])) return rc;
+  if (counts)
+    for (int i = 0; i < 4; ++i) counts[i] = k[i];
+  return SLIO_OK;
+}
+
+// one kind's transform, search and coefficient + rows launch, enqueued
+static int lmap_coeffs_enqueue(slio_lmap* m, int kind, const float transform[6]) {
+  Ctx& c = m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL]->c;
+  const int64_t n = c.n;
+  if (!c.wbx) {
+    const int64_t cap = c.prm.max_points;
+    hipError_t e;
+    if ((e = hipMalloc(&c.wbx, 4 * cap)) || (e = hipMalloc(&c.wby, 4 * cap)) || (e = hipMalloc(&c.wbz, 4 * cap))) {
+      set_error(std::string("slio_lmap_coeffs: hipMalloc: ") + hipGetErrorString(e));
+      return SLIO_ENOMEM;
+    }
+  }
+  if (n > 0) {
+    k_lmap_transform<<<grid_blocks(n), 256, 0, c.stream>>>(c.bx, c.by, c.bz, n, lmap_rot(transform), c.wbx, c.wby,
+                                                           c.wbz);
+    // the 5-NN of the map-frame points: the search pass in kNN-only mode with
+    // the identity pose, as slio_s2m_coeffs runs it
+    slio_pose idp{};
+    idp.rot[0] = 1.0;
+    idp.rli[0] = 1.0;
+    const PoseDev P = make_pose(&idp);
+    const ScanDev sd{c.wbx, c.wby, c.wbz, n};
+    if (int rc = enqueue_pass(c, &P, nullptr, 1, 0, nullptr, false, true, &sd)) return rc;
+    std::shared_lock<std::shared_mutex> lk(c.map->mu);
+    if (int rc = map_read_sync(c)) return rc;
+    // LMOptimization's trig, from transformTobeMapped[0..2] as written (:1457-1462)
+    S2mTrig T;
+    auto fc = [](float a) { return (float)std::cos((double)a); };
+    auto fs = [](float a) { return (float)std::sin((double)a); };
+    T.srx = fs(transform[0]), T.crx = fc(transform[0]);
+    T.sry = fs(transform[1]), T.cry = fc(transform[1]);
+    T.srz = fs(transform[2]), T.crz = fc(transform[2]);
+    const int nb = (int)((n + 255) / 256);
+    if (kind == 0)
+      k_lmap_coeff<0><<<nb, 256, 0, c.stream>>>(c.bx, c.by, c.bz, c.wbx, c.wby, c.wbz, n, c.nbr_pos, c.nbr_sqd,
+                                                c.map->pts, c.plane, c.sel, T, c.chunk_part);
+    else
+      k_lmap_coeff<1><<<nb, 256, 0, c.stream>>>(c.bx, c.by, c.bz, c.wbx, c.wby, c.wbz, n, c.nbr_pos, c.nbr_sqd,
+                                                c.map->pts, c.plane, c.sel, T, c.chunk_part);
+    SLIO_HIP(hipGetLastError());
+  }
+  c.s2m_kind = kind;
+  m->coeff_ok[kind] = true;
+  return SLIO_OK;
+}
+
+// the two kinds' partials summed in the fixed order (corners, then surfs)
+static int lmap_sum(slio_lmap* m, float AtA[36], float AtB[6], int64_t* nsel) {
+  double acc[kS2mSums] = {0};
+  for (int kind = 0; kind < 2; ++kind) {
+    Ctx& c = m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL]->c;
+    if (c.n == 0) continue;
+    const int nb = (int)((c.n + 255) / 256);
+    std::vector<double> part((size_t)nb * kS2mSums);
+    const Rb rb{part.data(), c.chunk_part, 8 * part.size()};
+    SLIO_HIP(readback(c.stream, &rb, 1));
+    for (int b = 0; b < nb; ++b)
+      for (int k = 0; k < kS2mSums; ++k) acc[k] = acc[k] + part[(size_t)b * kS2mSums + k];
+  }
+  int q = 0;
+  for (int r = 0; r < 6; ++r)
+    for (int cc = r; cc < 6; ++cc, ++q) AtA[6 * r + cc] = AtA[6 * cc + r] = (float)acc[q];
+  for (int r = 0; r < 6; ++r) AtB[r] = (float)acc[21 + r];
+  if (nsel) *nsel = (int64_t)llround(acc[27]);
+  return SLIO_OK;
+}
+
+static int lmap_coeff_state(slio_lmap* m, int kind, const char* who) {
+  Ctx& c = m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL]->c;
+  if (!c.map || !c.bx) {
+    set_error(std::string(who) + ": map and scan needed");
+    return SLIO_ESTATE;
+  }
+  return SLIO_OK;
+}
+
+extern "C" {
+
+int slio_lmap_params_default(slio_lmap_params* p) {
+  if (!p) {
+    set_error("slio_lmap_params_default: null");
+    return SLIO_EINVAL;
+  }
+  std::memset(p, 0, sizeof(*p));
+  p->device = 0;
+  p->max_points = 100000;
+  p->leaf_corner = 0.2f;
+  p->leaf_surf = 0.4f;
+  p->leaf_outlier = 0.4f;
+  p->pose_leaf = 1.0f;
+  p->search_radius = 50.0f;
+  p->max_iterations = 10;
+  p->mapping_interval = 0.3f;
+  p->scan_period = 0.1f;
+  p->keyframe_distance = 0.3f;
+  p->grid_cell = 0.0f;
+  return SLIO_OK;
+}
+
+int slio_lmap_destroy(slio_lmap_handle m) {
+  if (!m) return SLIO_OK;
+  int rc = SLIO_OK;
+  // (handle 0 owns the stream the others borrow: destroyed last)
+  for (int i = 3; i >= 0; --i)
+    if (m->h[i]) {
+      if (i > 0) (void)slio_set_stream(m->h[i], nullptr);
+      const int r = slio_destroy(m->h[i]);
+      if (r && !rc) rc = r;
+    }
+  delete m;
+  return rc;
+}
+
+int slio_lmap_create(slio_lmap_handle* out, const slio_lmap_params* p) {
+  if (!out || !p) {
+    set_error("slio_lmap_create: null argument");
+    return SLIO_EINVAL;
+  }
+  *out = nullptr;
+  if (p->max_points < 1 || !(p->leaf_corner > 0.0f) || !(p->leaf_surf > 0.0f) || !(p->leaf_outlier > 0.0f) ||
+      p->max_iterations < 0 || p->device < 0 || !(p->grid_cell >= 0.0f)) {
+    set_error("slio_lmap_create: bad max_points / leaves / max_iterations / device / grid_cell");
+    return SLIO_EINVAL;
+  }
+  auto* m = new slio_lmap();
+  m->prm = *p;
+  slio_params sp;
+  slio_params_default(&sp);
+  sp.device = p->device;
+  sp.max_points = p->max_points;
+  sp.grid_cell = p->grid_cell;
+  for (int i = 0; i < 4; ++i) {
+    int rc = slio_create(&m->h[i], &sp);
+    if (!rc && i > 0) rc = slio_set_stream(m->h[i], (void*)m->h[0]->c.stream);
+    if (!rc) rc = ensure_scan_buffers(m->h[i]->c);
+    if (rc) {
+      (void)slio_lmap_destroy(m);
+      return rc;
+    }
+  }
+  *out = m;
+  return SLIO_OK;
+}
+
+int slio_lmap_get_handle(slio_lmap_handle m, int which, slio_handle* out) {
+  if (int rc = lmap_check(m, "slio_lmap_get_handle")) return rc;
+  if (which < 0 || which > 3 || !out) {
+    set_error("slio_lmap_get_handle: bad arguments");
+    return SLIO_EINVAL;
+  }
+  // the caller may upload a scan or a map through it: nothing cached here survives that
+  m->coeff_ok[0] = m->coeff_ok[1] = false;
+  *out = m->h[which];
+  return SLIO_OK;
+}
+
+int slio_lmap_feed_lego(slio_lmap_handle m, void* lego, int64_t counts[4]) {
+  if (int rc = lmap_check(m, "slio_lmap_feed_lego")) return rc;
+  if (!lego) {
+    set_error("slio_lmap_feed_lego: null front-end handle");
+    return SLIO_EINVAL;
+  }
+  slio_lego_last_view v;
+  if (int rc = slio_lego_odom_last_view((slio_lego_handle)lego, &v)) return rc;
+  if (!v.published) {
+    set_error("slio_lmap_feed_lego: the last odometry call did not publish");
+    return SLIO_ESTATE;
+  }
+  if (v.device != m->prm.device) {
+    set_error("slio_lmap_feed_lego: the front-end is on another device");
+    return SLIO_EINVAL;
+  }
+  SLIO_HIP(hipSetDevice(m->prm.device));
+  return lmap_feed_dev(m, (const float4*)v.corner_xyzi, v.n_corner, (const float4*)v.surf_xyzi, v.n_surf,
+                       (const float4*)v.outlier_xyzi, v.n_outlier, counts);
+}
+
+int slio_lmap_feed_host(slio_lmap_handle m, const float* corner_xyzi, int64_t n_corner, const float* surf_xyzi,
+                        int64_t n_surf, const float* outlier_xyzi, int64_t n_outlier, int64_t counts[4]) {
+  if (int rc = lmap_check(m, "slio_lmap_feed_host")) return rc;
+  const float* src[3] = {corner_xyzi, surf_xyzi, outlier_xyzi};
+  const int64_t n[3] = {n_corner, n_surf, n_outlier};
+  for (int i = 0; i < 3; ++i)
+    if (n[i] < 0 || (n[i] > 0 && !src[i]) || n[i] > INT32_MAX) {
+      set_error("slio_lmap_feed_host: bad arguments");
+      return SLIO_EINVAL;
+    }
+  SLIO_HIP(hipSetDevice(m->prm.device));
+  // staged in the surf-total handle's temporaries (its own VoxelGrid runs last
+  // and uses pre[0] and pre[8..])
+  Ctx& ct = m->h[SLIO_LMAP_SURF_TOTAL]->c;
+  float4* d[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; ++i) {
+    if (n[i] == 0) continue;
+    hipError_t e;
+    if ((e = MapDev::take(ct.pre[1 + i], 16 * n[i]))) {
+      set_error(std::string("slio_lmap_feed_host: hipMalloc: ") + hipGetErrorString(e));
+      return SLIO_ENOMEM;
+    }
+    d[i] = (float4*)ct.pre[1 + i].p;
+    SLIO_HIP(hipMemcpyAsync(d[i], src[i], 16 * n[i], hipMemcpyHostToDevice, ct.stream));
+  }
+  return lmap_feed_dev(m, d[0], n[0], d[1], n[1], d[2], n[2], counts);
+}
+
+int slio_lmap_extract(slio_lmap_handle m, const int32_t* key_ind, int32_t nsel, int64_t counts[4]) {
+  static const char* who = "slio_lmap_extract";
+  if (int rc = lmap_check(m, who)) return rc;
+  if (nsel < 0 || (nsel > 0 && !key_ind)) {
+    set_error("slio_lmap_extract: bad arguments");
+    return SLIO_EINVAL;
+  }
+  Ctx& cc = m->h[SLIO_LMAP_CORNER]->c;
+  Ctx& ct = m->h[SLIO_LMAP_SURF_TOTAL]->c;
+  const int32_t nkeys = (int32_t)(m->poses6.size() / 6);
+  std::vector<float> poses((size_t)nsel * 6);
+  for (int32_t i = 0; i < nsel; ++i) {
+    if (key_ind[i] < 0 || key_ind[i] >= nkeys) {
+      set_error("slio_lmap_extract: key index " + std::to_string(key_ind[i]) + " out of range");
+      return SLIO_EINVAL;
+    }
+    std::memcpy(&poses[6 * (size_t)i], &m->poses6[6 * (size_t)key_ind[i]], 24);
+  }
+  std::vector<KfSeg> segc, segs;
+  int64_t nc = 0, ns = 0;
+  const Ctx* srcc[1] = {&cc};
+  const Ctx* srcs[2] = {&m->h[SLIO_LMAP_SURF]->c, &m->h[SLIO_LMAP_OUTLIER]->c};
+  if (int rc = kf_segments(srcc, 1, key_ind, poses.data(), nsel, segc, nc, who, 1)) return rc;
+  if (int rc = kf_segments(srcs, 2, key_ind, poses.data(), nsel, segs, ns, who, 1)) return rc;
+  SLIO_HIP(hipSetDevice(m->prm.device));
+  m->coeff_ok[0] = m->coeff_ok[1] = false;
+  int64_t k[4] = {0, 0, 0, 0};
+  if (int rc = kf_assemble(cc, segc, nc, m->prm.leaf_corner, false, k, who, 1)) return rc;
+  if (int rc = kf_assemble(ct, segs, ns, m->prm.leaf_surf, false, k + 2, who, 1)) return rc;
+  if (counts)
+    for (int i = 0; i < 4; ++i) counts[i] = k[i];
+  return SLIO_OK;
+}
+
+int slio_lmap_coeffs(slio_lmap_handle m, int kind, const float transform[6], int64_t* nsel) {
+  if (int rc = lmap_check(m, "slio_lmap_coeffs")) return rc;
+  if ((kind != 0 && kind != 1) || !transform) {
+    set_error("slio_lmap_coeffs: bad arguments");
+    return SLIO_EINVAL;
+  }
+  if (int rc = lmap_coeff_state(m, kind, "slio_lmap_coeffs")) return rc;
+  SLIO_HIP(hipSetDevice(m->prm.device));
+  if (int rc = lmap_coeffs_enqueue(m, kind, transform)) return rc;
+  if (nsel) {
+    Ctx& c = m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL]->c;
+    std::vector<uint8_t> sl((size_t)c.n);
+    if (c.n) {
+      SLIO_HIP(hipStreamSynchronize(c.stream));
+      SLIO_HIP(hipMemcpy(sl.data(), c.sel, c.n, hipMemcpyDeviceToHost));
+    }
+    int64_t k = 0;
+    for (uint8_t v : sl) k += v;
+    *nsel = k;
+  }
+  return SLIO_OK;
+}
+
+int slio_lmap_get_coeffs(slio_lmap_handle m, int kind, float* coeff, uint8_t* sel) {
+  if (int rc = lmap_check(m, "slio_lmap_get_coeffs")) return rc;
+  if (kind != 0 && kind != 1) {
+    set_error("slio_lmap_get_coeffs: bad arguments");
+    return SLIO_EINVAL;
+  }
+  if (!m->coeff_ok[kind]) {
+    set_error("slio_lmap_get_coeffs: no coefficients of that kind");
+    return SLIO_ESTATE;
+  }
+  return slio_s2m_get_coeffs(m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL], coeff, sel);
+}
+
+int slio_lmap_normal_equations(slio_lmap_handle m, float AtA[36], float AtB[6], int64_t* nsel) {
+  if (int rc = lmap_check(m, "slio_lmap_normal_equations")) return rc;
+  if (!AtA || !AtB) {
+    set_error("slio_lmap_normal_equations: bad arguments");
+    return SLIO_EINVAL;
+  }
+  if (!m->coeff_ok[0] || !m->coeff_ok[1]) {
+    set_error("slio_lmap_normal_equations: slio_lmap_coeffs of both kinds first");
+    return SLIO_ESTATE;
+  }
+  SLIO_HIP(hipSetDevice(m->prm.device));
+  return lmap_sum(m, AtA, AtB, nsel);
+}
+
+int slio_lmap_optimize(slio_lmap_handle m, float transform[6], int32_t* iterations, int32_t* is_degenerate) {
+  if (int rc = lmap_check(m, "slio_lmap_optimize")) return rc;
+  if (!transform || !iterations || !is_degenerate) {
+    set_error("slio_lmap_optimize: bad arguments");
+    return SLIO_EINVAL;
+  }
+  for (int kind = 0; kind < 2; ++kind)
+    if (int rc = lmap_coeff_state(m, kind, "slio_lmap_optimize")) return rc;
+  *iterations = 0;
+  *is_degenerate = 0;
+  // :1606
+  if (!(m->h[SLIO_LMAP_CORNER]->c.map->n > 10 && m->h[SLIO_LMAP_SURF_TOTAL]->c.map->n > 100)) return SLIO_OK;
+  SLIO_HIP(hipSetDevice(m->prm.device));
+  float matP[36] = {0};
+  int deg = 0;
+  for (int it = 0; it < m->prm.max_iterations; ++it) {
+    if (int rc = lmap_coeffs_enqueue(m, 0, transform)) return rc;
+    if (int rc = lmap_coeffs_enqueue(m, 1, transform)) return rc;
+    float AtA[36], AtB[6];
+    int64_t nsel = 0;
+    if (int rc = lmap_sum(m, AtA, AtB, &nsel)) return rc;
+    int conv = 0;
+    const int rc = slio_s2m_lm_step(AtA, AtB, nsel, it, transform, &deg, matP, &conv);
+    if (rc < 0) return rc;
+    *iterations = it + 1;
+    if (conv) break;
+  }
+  *is_degenerate = deg;
+  return SLIO_OK;
+}
+
+int slio_lmap_save_keyframe(slio_lmap_handle m, const float pose6[6], int32_t* key) {
+  if (int rc = lmap_check(m, "slio_lmap_save_keyframe")) return rc;
+  if (!pose6) {
+    set_error("slio_lmap_save_keyframe: null pose");
+    return SLIO_EINVAL;
+  }
+  const int which[3] = {SLIO_LMAP_CORNER, SLIO_LMAP_SURF, SLIO_LMAP_OUTLIER};
+  int32_t k = -1;
+  for (int w : which) {
+    int32_t kk = -1;
+    if (int rc = slio_s2m_kf_push_scan(m->h[w], &kk)) return rc;
+    k = kk;
+  }
+  m->poses6.insert(m->poses6.end(), pose6, pose6 + 6);
+  if (key) *key = k;
+  return SLIO_OK;
+}
+
+int slio_lmap_get_key_poses(slio_lmap_handle m, float* poses6, int32_t cap, int32_t* nkeys) {
+  if (int rc = lmap_check(m, "slio_lmap_get_key_poses")) return rc;
+  const int32_t nk = (int32_t)(m->poses6.size() / 6);
+  if (nkeys) *nkeys = nk;
+  if (poses6) {
+    if (cap < nk) {
+      set_error("slio_lmap_get_key_poses: buffer too small");
+      return SLIO_ECAPACITY;
+    }
+    if (nk) std::memcpy(poses6, m->poses6.data(), sizeof(float) * m->poses6.size());
+  }
+  return SLIO_OK;
+}
+
+int slio_lmap_clear(slio_lmap_handle m) {
+  if (int rc = lmap_check(m, "slio_lmap_clear")) return rc;
+  const int which[3] = {SLIO_LMAP_CORNER, SLIO_LMAP_SURF, SLIO_LMAP_OUTLIER};
+  for (int w : which)
+    if (int rc = slio_s2m_kf_clear(m->h[w])) return rc;
+  m->poses6.clear();
+  m->coeff_ok[0] = m->coeff_ok[1] = false;
+  return SLIO_OK;
 }
 
 }  // extern "C"

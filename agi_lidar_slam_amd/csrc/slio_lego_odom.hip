@@ -832,6 +832,27 @@ int slio_lego_odom_get_last(slio_lego_handle h, float* corner_xyzi, float* surf_
   return SLIO_OK;
 }
 
+int slio_lego_odom_last_view(slio_lego_handle h, slio_lego_last_view* view) {
+  if (!view) {
+    set_error("slio_lego_odom_last_view: null");
+    return SLIO_EINVAL;
+  }
+  ODOM_CHECK(h, v, o, "slio_lego_odom_last_view");
+  slio_lego_odom_out r;
+  ODOM_HIP(hipMemcpyAsync(&r, &o->dev->out, sizeof(r), hipMemcpyDeviceToHost, v.stream));
+  ODOM_HIP(hipStreamSynchronize(v.stream));
+  std::memset(view, 0, sizeof(*view));
+  view->corner_xyzi = reinterpret_cast<const float*>(o->corner_last);
+  view->surf_xyzi = reinterpret_cast<const float*>(o->surf_last);
+  view->outlier_xyzi = reinterpret_cast<const float*>(o->outlier_last);
+  view->n_corner = r.n_corner_last;
+  view->n_surf = r.n_surf_last;
+  view->n_outlier = r.n_outlier_last;
+  view->published = o->inited ? r.published : 0;
+  view->device = v.device;
+  return SLIO_OK;
+}
+
 int slio_lego_odom_get_state(slio_lego_handle h, slio_lego_odom_state* s) {
   ODOM_CHECK(h, v, o, "slio_lego_odom_get_state");
   if (!s) {

@@ -21,6 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
+from .lego_map import LegoMapping, TransformFusion, extract_surrounding  # noqa: F401  (the mapping back-end)
 
 IMU_QUE_LEN = 200  # imuQueLength (utility.h:42)
 

@@ -617,6 +617,157 @@ int slio_icp_state_init(slio_icp_state* s, const float guess[16]);
 int slio_icp_step(const double sums[16], int64_t ncorr, const slio_icp_params* params,
                   slio_icp_state* state, float delta[16], int* done);
 
+/* ---- LeGO-LOAM mapping (src/LeGO-LOAM/LeGO-LOAM/src/mapOptmization.cpp with
+ *      loopClosureEnableFlag = false, and transformFusion.cpp) ----------------
+ * One opaque mapper owns four single-rank handles on one device and one
+ * stream: SLIO_LMAP_CORNER (laserCloudCornerFromMapDS, laserCloudCornerLastDS,
+ * cornerCloudKeyFrames), SLIO_LMAP_SURF_TOTAL (laserCloudSurfFromMapDS,
+ * laserCloudSurfTotalLastDS), SLIO_LMAP_SURF (laserCloudSurfLastDS,
+ * surfCloudKeyFrames) and SLIO_LMAP_OUTLIER (laserCloudOutlierLastDS,
+ * outlierCloudKeyFrames).  Everything is in LeGO-LOAM's camera-like frame;
+ * poses are {rx, ry, rz, tx, ty, tz} (transformTobeMapped's layout); no axis
+ * swap appears anywhere.  Argument errors are reported before any device call.
+ *
+ * Stated departures from the reference:
+ *  - the 5-NN is exact and ties at equal float distance go to the lower
+ *    position in the map's cell-sorted order (slio_get_neighbors), where
+ *    FLANN's order is not pinned by anything;
+ *  - inside a voxel the points are summed in ascending position of the input
+ *    (slio_scan_upload_voxel's VoxelGrid semantics);
+ *  - sin / cos / atan2 / asin of a float are the double functions rounded to
+ *    float;
+ *  - the key pose is transformTobeMapped itself.  The reference passes it
+ *    through an iSAM2 chain of one prior and successive between-factors
+ *    (:1656-1749); without loop closures that chain's optimum is the composed
+ *    odometry, so GTSAM returns the same pose up to its own rounding and
+ *    :1737-1749 write that value back.  GTSAM is absent here;
+ *  - the reference's cache of transformed keyframes (surrounding*CloudKeyFrames)
+ *    is not mirrored: without loop closure a key's pose never changes, so
+ *    transforming it again gives the same floats.  The cache's list order,
+ *    which fixes the concatenation order, is kept (the caller's key list). */
+typedef struct slio_lmap* slio_lmap_handle;
+enum { SLIO_LMAP_CORNER = 0, SLIO_LMAP_SURF_TOTAL = 1, SLIO_LMAP_SURF = 2, SLIO_LMAP_OUTLIER = 3 };
+typedef struct slio_lmap_params {
+  int32_t device;
+  int32_t max_points;          /* capacity of every downsampled scan cloud               */
+  float leaf_corner;           /* downSizeFilterCorner, 0.2 (:265)                       */
+  float leaf_surf;             /* downSizeFilterSurf, 0.4 (:266)                         */
+  float leaf_outlier;          /* downSizeFilterOutlier, 0.4 (:267)                      */
+  float pose_leaf;             /* downSizeFilterSurroundingKeyPoses, 1.0 (:274)          */
+  float search_radius;         /* surroundingKeyframeSearchRadius, 50 (utility.h:79)     */
+  int32_t max_iterations;      /* the 10 of scan2MapOptimization (:1612)                 */
+  float mapping_interval;      /* mappingProcessInterval, 0.3 (utility.h:31)             */
+  float scan_period;           /* scanPeriod, 0.1 (utility.h:28)                         */
+  float keyframe_distance;     /* the 0.3 m of saveKeyFramesAndFactor (:1639)            */
+  float grid_cell;             /* slio_params.grid_cell of the two map handles (0: auto) */
+  int32_t reserved[4];
+} slio_lmap_params;
+int slio_lmap_params_default(slio_lmap_params* p);
+int slio_lmap_create(slio_lmap_handle* out, const slio_lmap_params* p);
+int slio_lmap_destroy(slio_lmap_handle m);
+/* One of the four handles (SLIO_LMAP_*), for the getters this library already
+ * has -- slio_scan_download, slio_map_download, slio_map_info,
+ * slio_get_neighbors, slio_far_queries, slio_s2m_kf_info / _sizes / _get --
+ * and, for tests and users without the front-end, slio_map_upload /
+ * slio_scan_upload in place of slio_lmap_extract / slio_lmap_feed_*.  The
+ * mapper keeps ownership. */
+int slio_lmap_get_handle(slio_lmap_handle m, int which, slio_handle* out);
+/* downsampleCurrentScan (:1197-1220), device to device, from the front-end's
+ * published last clouds (slio_lego_odom_last_view, slio_frontend.h):
+ * cornerLastDS = VoxelGrid(corner, leaf_corner), surfLastDS = VoxelGrid(surf,
+ * leaf_surf), outlierLastDS = VoxelGrid(outlier, leaf_outlier), surfTotalLastDS
+ * = VoxelGrid(surfLastDS ++ outlierLastDS, leaf_surf), each under
+ * slio_scan_upload_voxel's semantics.  No point crosses PCIe; the host waits
+ * for each grid's voxel count.  The front-end's buffers have been read when
+ * the call returns.  counts = the four clouds' sizes in SLIO_LMAP_* order.
+ * `lego` is a slio_lego_handle.  ESTATE when its last odometry call did not
+ * publish (or the odometry is not enabled); EINVAL for another device. */
+int slio_lmap_feed_lego(slio_lmap_handle m, void* lego, int64_t counts[4]);
+/* The same from three host clouds (n x {x, y, z, intensity}, the layout of
+ * slio_lego_odom_get_last). */
+int slio_lmap_feed_host(slio_lmap_handle m, const float* corner_xyzi, int64_t n_corner,
+                        const float* surf_xyzi, int64_t n_surf, const float* outlier_xyzi,
+                        int64_t n_outlier, int64_t counts[4]);
+/* extractSurroundingKeyFrames' cloud work (:1166-1194): for i in list order
+ * key key_ind[i] (surroundingExistingKeyPosesID; a key may repeat) goes
+ * through transformPointCloud (:624-652: yaw about z, roll about x, pitch
+ * about y in float, then the translation) with its pose from the mapper's own
+ * key-pose table.  Corner map = the keys' corner clouds; surf map = each
+ * key's surf cloud followed by its outlier cloud (:1179-1183).  Both are
+ * downsampled (leaf_corner / leaf_surf) and indexed in place as
+ * slio_s2m_map_from_keyframes does.  counts = {corner points concatenated,
+ * corner map points, surf points concatenated, surf map points}.  EINVAL for
+ * a key out of range. */
+int slio_lmap_extract(slio_lmap_handle m, const int32_t* key_ind, int32_t nsel, int64_t counts[4]);
+/* cornerOptimization (kind 0, :1222-1370) / surfOptimization (kind 1,
+ * :1372-1450) at transformTobeMapped = transform, and LMOptimization's rows
+ * (:1477-1537) of the selected points with their per-workgroup fp64 partial
+ * sums, after the search in one launch.  The plane of kind 1 is
+ * cv::solve(DECOMP_QR) on the 5 x 3 system (:1395) as slio_cvsolve.hpp
+ * restates it; a failed solve leaves x = 0, the NaNs that follow unselect the
+ * point.  nsel may be NULL (no wait then).  EINVAL: kind outside {0, 1};
+ * ESTATE: no map or no scan of that kind. */
+int slio_lmap_coeffs(slio_lmap_handle m, int kind, const float transform[6], int64_t* nsel);
+/* The kind's coefficients (n x 4) and flags of the last slio_lmap_coeffs. */
+int slio_lmap_get_coeffs(slio_lmap_handle m, int kind, float* coeff, uint8_t* sel);
+/* A^T A / A^T B of the rows the last slio_lmap_coeffs of BOTH kinds left (at
+ * the transform given there): fp64 sums in k_s2m_rows' fixed tree -- a
+ * butterfly per wavefront, the four wavefronts in order, workgroups in order,
+ * corners before surfs -- rounded to float.  ESTATE unless both kinds'
+ * coefficients are current (an empty scan counts as current once computed). */
+int slio_lmap_normal_equations(slio_lmap_handle m, float AtA[36], float AtB[6], int64_t* nsel);
+/* scan2MapOptimization's loop (:1606-1621) on the same kernels: runs only when
+ * the corner map holds more than 10 points and the surf map more than 100
+ * (else *iterations = 0 and transform is untouched); at most max_iterations
+ * turns of coeffs(0), coeffs(1), normal equations (one wait) and
+ * slio_s2m_lm_step -- which, read beside LMOptimization :1539-1600, is the same
+ * function (QR solve, eigenvalue threshold 100, the 50-row gate, 0.05 / 0.05).
+ * *iterations = turns executed.  transformUpdate is the caller's
+ * (slio_lmap_transform_update). */
+int slio_lmap_optimize(slio_lmap_handle m, float transform[6], int32_t* iterations, int32_t* is_degenerate);
+/* saveKeyFramesAndFactor's cloud copies (:1751-1766): cornerLastDS, surfLastDS
+ * and outlierLastDS become keyframe *key of the three stores by
+ * device-to-device copies, pose6 its entry of the key-pose table
+ * (cloudKeyPoses6D; see the departure above).  Before any feed the three
+ * clouds are empty, which is a valid keyframe. */
+int slio_lmap_save_keyframe(slio_lmap_handle m, const float pose6[6], int32_t* key);
+/* cloudKeyPoses6D: nkeys x 6; ECAPACITY if cap < nkeys.  poses6 may be NULL. */
+int slio_lmap_get_key_poses(slio_lmap_handle m, float* poses6, int32_t cap, int32_t* nkeys);
+/* Forget every keyframe and key pose (the stores' arenas stay allocated). */
+int slio_lmap_clear(slio_lmap_handle m);
+/* -- host only, callable without a GPU -- */
+/* transformAssociateToMap (mapOptmization.cpp:394-519; transformFusion.cpp
+ * :91-215 is the same formula writing transformMapped): float arithmetic in
+ * the reference's expression order. */
+int slio_lmap_associate_to_map(const float transform_sum[6], const float transform_bef_mapped[6],
+                               const float transform_aft_mapped[6], float transform_tobe_mapped[6]);
+/* transformUpdate (:521-560): the IMU blend 0.998 / 0.002 on rx (pitch) and rz
+ * (roll) from the ring (imu_time, imu_roll, imu_pitch)[imu_len] with
+ * imuPointerLast = imu_last (< 0: no IMU) and *imu_front = imuPointerFront
+ * (in/out), interpolated at time_odometry + scan_period; then bef = sum,
+ * aft = tobe. */
+int slio_lmap_transform_update(float transform_tobe_mapped[6], const float transform_sum[6],
+                               double time_odometry, float scan_period, const double* imu_time,
+                               const float* imu_roll, const float* imu_pitch, int32_t imu_len,
+                               int32_t imu_last, int32_t* imu_front, float transform_bef_mapped[6],
+                               float transform_aft_mapped[6]);
+/* transformFusion.cpp's state: laserOdometryHandler (:217-254) = fuse with
+ * aft == NULL: transformSum = sum, transformMapped from the triple;
+ * odomAftMappedHandler (:256-277) = sum == NULL: stores aft / bef. */
+typedef struct slio_lmap_fusion {
+  float transform_sum[6], transform_bef_mapped[6], transform_aft_mapped[6], transform_mapped[6];
+} slio_lmap_fusion;
+int slio_lmap_fuse(slio_lmap_fusion* f, const float transform_sum[6], const float aft_mapped[6],
+                   const float bef_mapped[6]);
+/* saveKeyFramesAndFactor's decision (:1629-1645): *save = 1 for the first
+ * frame (nkeys == 0) or when the float distance |cur - prev| is not below
+ * `distance` (the reference's double 0.3). */
+int slio_lmap_keyframe_decision(const float prev_pos[3], const float cur_pos[3], int32_t nkeys,
+                                double distance, int* save);
+/* The M x N QR of slio_cvsolve.hpp for tests: (m, n) in {(5, 3), (3, 3),
+ * (6, 6)}; returns 1 where the solve gives up (x zeroed). */
+int slio_lmap_qr_solve(int m, int n, const float* A, const float* b, float* x);
+
 /* Manifold helpers exported for tests (esekfom.hpp:59-73, 236-258). */
 int slio_state_boxplus(const slio_state* x, const double dx[24], slio_state* out);
 int slio_state_boxminus(const slio_state* x1, const slio_state* x2, double dx[24]);

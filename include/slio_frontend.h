@@ -286,6 +286,22 @@ int slio_lego_odom_run(slio_lego_handle h, slio_lego_odom_out* out);
  * [n_outlier_last * 4].  Any may be NULL. */
 int slio_lego_odom_get_last(slio_lego_handle h, float* corner_xyzi, float* surf_xyzi, float* outlier_xyzi);
 
+/* Device views of the same three clouds (float4 xyzi) for a consumer on the
+ * device (slio_lmap_feed_lego, slio.h): waits for the handle's stream, so the
+ * clouds are complete when it returns; they stay valid until the next sweep
+ * or odometry call on this handle.  published = the last odometry call's gate
+ * (the outlier cloud is current only then). */
+typedef struct slio_lego_last_view {
+  const float* corner_xyzi;
+  const float* surf_xyzi;
+  const float* outlier_xyzi;
+  int32_t n_corner, n_surf, n_outlier;
+  int32_t published;
+  int32_t device;
+  int32_t reserved;
+} slio_lego_last_view;
+int slio_lego_odom_last_view(slio_lego_handle h, slio_lego_last_view* view);
+
 /* Lockstep / test entries: the same kernels and the same step code, one host
  * wait per call. */
 /* Replaces cornerPointsSharp, surfPointsFlat and the two last clouds (xyzi)

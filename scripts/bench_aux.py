@@ -17,6 +17,10 @@
   lego_odom LeGO-LOAM front-end + scan-to-scan odometry on a 16 x 1800 sequence:
             sweeps per second, the odometry call alone, the lockstep loop and
             the numpy restatement (only when named)
+  lego_map  LeGO-LOAM mapping back-end (LegoMapping) behind the front-end and
+            odometry on the same sequence: ms per mapping call and its split,
+            iterations, map sizes, the host restatement beside it (only when
+            named)
 One JSON line per measurement (host wall clock around synchronous calls)."""
 import ctypes as C
 import json
@@ -440,8 +444,94 @@ def lego_odom(sweeps=12, restate=True):
     fe.close()
 
 
+def lego_map(calls=8, restate=True):
+    """LeGO-LOAM mapping (LegoMapping: slio_lmap_*) behind the front-end and
+    odometry on the 16 x 1800 sequence of lego_odom: ms per mapping call and
+    its split (downsampleCurrentScan from the device clouds,
+    extractSurroundingKeyFrames, scan2MapOptimization, saveKeyFramesAndFactor),
+    iterations, map and scan sizes, whether the searches took the far path;
+    the first call apart (it allocates); and the last call once more through
+    the host restatement (tests/lego_map_model.py: numpy, the oracle's kd-tree
+    and VoxelGrid) on the same data."""
+    import lego_map_model as M
+    from oracle import oracle as O
+    from test_lego_odom_cpu import SWEEP_T, moving_sweep
+    from agi_lidar_slam_amd.lego import LegoFrontEnd, LegoMapping, LegoParams
+    from agi_lidar_slam_amd.lego_map import CORNER, OUTLIER, SURF, SURF_TOTAL
+    O.build()
+    fe = LegoFrontEnd(LegoParams())
+    fe.enable_odometry()
+    mp = LegoMapping(max_points=20000)
+    rows, host, k = [], None, 0
+    while len(rows) < calls and k < 10 * calls:
+        sc = moving_sweep(k, horizon=1800)
+        out = fe.runFeatureAssociation(sc["x"], sc["y"], sc["z"], None, k * SWEEP_T)
+        t = (k + 1) * SWEEP_T
+        k += 1
+        if not out["published"]:
+            continue
+        mp.laserOdometryHandler(out["transform_sum"], t)
+        if not (t - mp.timeLastProcessing >= float(np.float32(mp.params.mapping_interval))):
+            continue
+        mp.timeLastProcessing = t
+        t0 = time.perf_counter()
+        tobe0 = mp.transformAssociateToMap()
+        t1 = time.perf_counter()
+        mp.extractSurroundingKeyFrames()
+        t2 = time.perf_counter()
+        mp.downsampleCurrentScan(fe)
+        t3 = time.perf_counter()
+        mp.scan2MapOptimization()
+        t4 = time.perf_counter()
+        far = [mp.far_queries(0), mp.far_queries(1)] if mp.iterations else [0, 0]
+        if restate and len(rows) == calls - 1:
+            # the same call on the host, before the keyframe is saved
+            last = fe.last_clouds()
+            cl, sl, ol = (last[n][:, :3] for n in ("laserCloudCornerLast", "laserCloudSurfLast", "outlierCloudLast"))
+            keys = list(mp.surroundingExistingKeyPosesID)
+            kf = {kk: [mp.keyframe(w, kk) for w in (CORNER, SURF, OUTLIER)] for kk in set(keys)}
+            poses = mp.cloudKeyPoses6D
+            h0 = time.perf_counter()
+            cds, sds, ods = O.voxel_grid(cl, 0.2), O.voxel_grid(sl, 0.4), O.voxel_grid(ol, 0.4)
+            tds = O.voxel_grid(np.concatenate([sds, ods]), 0.4)
+            h1 = time.perf_counter()
+            cmap = O.voxel_grid(np.concatenate([M.to_map(poses[kk], kf[kk][0]) for kk in keys]), 0.2)
+            smap = O.voxel_grid(np.concatenate([M.to_map(poses[kk], kf[kk][j]) for kk in keys for j in (1, 2)]), 0.4)
+            h2 = time.perf_counter()
+            tm, im, _, _ = M.scan2map(tobe0, cds, tds, cmap, smap, lambda m_, q: O.Tree(m_).knn(q, 5))
+            h3 = time.perf_counter()
+            host = dict(ms_feed=(h1 - h0) * 1e3, ms_extract=(h2 - h1) * 1e3, ms_optimise=(h3 - h2) * 1e3,
+                        ms_call=(h3 - h0) * 1e3, iterations=im,
+                        same_bits_as_device=bool(np.array_equal(tm, mp.transformTobeMapped) or mp.imuPointerLast >= 0),
+                        same_clouds=bool(np.array_equal(cds, mp.scan(CORNER)) and np.array_equal(tds, mp.scan(SURF_TOTAL))
+                                         and np.array_equal(cmap, mp.map_points(0))
+                                         and np.array_equal(smap, mp.map_points(1))))
+        t5 = time.perf_counter()
+        mp.saveKeyFramesAndFactor()
+        t6 = time.perf_counter()
+        rows.append(dict(ms_call=(t4 - t0 + t6 - t5) * 1e3, ms_associate=(t1 - t0) * 1e3, ms_extract=(t2 - t1) * 1e3,
+                         ms_feed=(t3 - t2) * 1e3, ms_optimise=(t4 - t3) * 1e3, ms_save=(t6 - t5) * 1e3,
+                         iterations=mp.iterations, far_queries_last_pass=far, keys=len(mp.surroundingExistingKeyPosesID),
+                         map_counts=[int(v) for v in mp.map_counts], scan_counts=[int(v) for v in mp.scan_counts],
+                         saved=mp.saved_last))
+    later = rows[1:]
+    mean = lambda key: float(np.mean([r[key] for r in later]))  # noqa: E731
+    print(json.dumps({
+        "bench": "lego_map", "n_scan": 16, "horizon_scan": 1800, "sweeps": k, "mapping_calls": len(rows),
+        "first_call": rows[0],
+        "mean_after_first": {key: mean(key) for key in ("ms_call", "ms_associate", "ms_extract", "ms_feed",
+                                                        "ms_optimise", "ms_save", "iterations")},
+        "last_call": rows[-1], "keyframes": int(mp.cloudKeyPoses6D.shape[0]),
+        "far_path_used": bool(any(sum(r["far_queries_last_pass"]) for r in rows)),
+        "host_restatement_last_call": host, "kernel_times": "not measured"}), flush=True)
+    mp.close()
+    fe.close()
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "lego_map" in what:
+        lego_map()
     if "lego_odom" in what:
         lego_odom()
     if "s2m_loop" in what:
