@@ -16,9 +16,10 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libslio.so")
 
-SOURCES = ["slio_device.hip", "slio_ikf.cpp", "slio_imu.cpp", "slio_s2m.cpp", "slio_lio.hip",
+SOURCES = ["slio_device.hip", "slio_mapopt.hip", "slio_ikf.cpp", "slio_imu.cpp", "slio_s2m.cpp", "slio_lio.hip",
            "slio_lego_odom.hip", "slio_lmap.cpp"]
-HEADERS = ["slio_common.hpp", "slio_plane.hpp", "slio_so3.hpp", "slio_cvsolve.hpp", "slio_lego_odom.hpp"]
+HEADERS = ["slio_common.hpp", "slio_plane.hpp", "slio_so3.hpp", "slio_cvsolve.hpp", "slio_lego_odom.hpp",
+           "slio_device.hpp", "slio_search.hpp"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -65,7 +66,7 @@ def _stale() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile every source to an object in parallel (the two HIP files take
+    """Compile every source to an object in parallel (the HIP files take
     most of the time), then link the shared library."""
     if not force and not _stale():
         return LIB

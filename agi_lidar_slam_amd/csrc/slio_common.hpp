@@ -2,6 +2,7 @@
 // (slio_device.hip) and the host IKF driver (slio_ikf.cpp).
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 
@@ -17,6 +18,11 @@ namespace slio {
 
 // thread-local last-error message behind slio_last_error()
 void set_error(const std::string& msg);
+
+// sin / cos of a float as the references' x86-64 builds have them: the double
+// function, rounded to float (host and device)
+SLIO_HD inline float fsin(float a) { return (float)sin((double)a); }
+SLIO_HD inline float fcos(float a) { return (float)cos((double)a); }
 
 // Reduction product table: product k accumulates row[pa[k]] * row[pb[k]]
 // over the selected points of a pass, where the per-point row is

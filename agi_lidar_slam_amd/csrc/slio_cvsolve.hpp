@@ -4,7 +4,7 @@
 // (slio_s2m.cpp), 3 for LeGO-LOAM's two-stage scan-to-scan step, which is
 // written here once for the host entry (slio_lego_odom_step) and for the
 // device loop (slio_lego_odom.hip); 5 x 3 for the plane fit of LeGO-LOAM's
-// mapping (slio_device.hip, k_lmap_coeff).  OpenCV is third-party and absent:
+// mapping (slio_mapopt.hip, k_lmap_coeff). OpenCV is third-party and absent:
 // what is written here is the specification of these solvers.
 #pragma once
 

@@ -14,6 +14,9 @@
 //     so 1/2/4/8 GPUs give bitwise-identical sums.
 // Built with -ffp-contract=off: every float/double expression is evaluated
 // exactly as written (the reference's x86-64 build has no FMA either).
+// The mapping back-ends built on this core (LIO-SAM scan-to-map, loop closure
+// and keyframe store, LeGO-LOAM mapping) are in slio_mapopt.hip; what they use
+// of it is declared in slio_device.hpp and slio_search.hpp.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -36,6 +39,7 @@
 
 #include "slio_common.hpp"
 #include "slio_cvsolve.hpp"
+#include "slio_device.hpp"
 #include "slio_frontend.h"
 #include "slio_plane.hpp"
 #include "slio_so3.hpp"
@@ -61,21 +65,11 @@ namespace slio {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
-#define SLIO_HIP(call)                                                          \
-  do {                                                                          \
-    hipError_t e_ = (call);                                                     \
-    if (e_ != hipSuccess) {                                                     \
-      set_error(std::string(#call) + ": " + hipGetErrorString(e_));             \
-      return SLIO_EDEVICE;                                                      \
-    }                                                                           \
-  } while (0)
-
 constexpr int kBlock = 256;                      // threads per search workgroup
 constexpr int kDefaultLPQ = 2;                   // lanes per query (tuned on MI355X)
 #ifndef SLIO_SEARCH_U
 #define SLIO_SEARCH_U 3                          // candidate loads in flight per lane and step (A/B on MI355X, block rows: 3 < 4 < 2)
 #endif
-constexpr uint64_t kInfKey = ~0ull;
 
 #ifdef SLIO_ABL_STAMP
 // diagnostic build only: per-block phase timestamps (s_memrealtime, 100 MHz)
@@ -143,147 +137,6 @@ __constant__ uint8_t c_pa[SLIO_NPROD];
 __constant__ uint8_t c_pb[SLIO_NPROD];
 
 // ---------------------------------------------------------------- map index
-struct GridGeom {
-  float ox, oy, oz;   // origin = bbox min
-  float h, inv_h;     // cell edge and its reciprocal
-  float tol;          // conservative slack on cell-boundary coordinates
-  int dx, dy, dz;     // dims
-};
-
-// Coarse level for the queries the fine grid cannot finish cheaply (5th
-// neighbour beyond the 5x5x5 fine cube, query cells outside the grid): cells
-// of edge 4h on the fine grid's origin -- coarse cell (cx, cy, cz) is the fine
-// cells [4cx, 4cx + 4) x [4cy, 4cy + 4) x [4cz, 4cz + 4), so its points are 16
-// runs of the fine cell-sorted pts (one per fine (y, z) row) -- and a bounding
-// box of every coarse cell's points: exact pruning, since a float distance to
-// a point is never below the float distance to a box that contains it, both
-// rounded monotonically.  An upload or a sorting rebuild makes the boxes
-// tight; a merge rebuild (the live map) only widens them by its additions
-// (k_coarse_extend): a deleted point leaves a box merely conservative.  No
-// coarse copy of the points, so a merge rebuild does not rewrite one.
-struct CoarseView {
-  GridGeom g;               // h = 4 x the fine cell edge
-  const float4* lo;         // per coarse cell: min x, y, z, bits(points ever counted: 0 = empty)
-  const float4* hi;         // per coarse cell: max x, y, z
-};
-
-struct Ctx;
-
-struct MapDev {
-  GridGeom g;
-  int64_t n = 0;
-  int64_t ncells = 0;
-  float4* pts = nullptr;          // sorted by cell: x, y, z, bits(map index)
-  uint32_t* start = nullptr;      // ncells + 1 prefix offsets
-  // coarse level (CoarseView)
-  GridGeom cg;
-  int64_t nccells = 0;
-  float4* clo = nullptr;
-  float4* chi = nullptr;
-  // block rows (optional, ~9x the points): entry (x, y, z) holds the points
-  // of the 9 cells (x, y + j, z + k), j, k in {-1, 0, 1}, with .w = their
-  // position in pts; entries are laid out in cell order, so the 3x3x3 block
-  // around a cell is ONE contiguous range [bstart[c - 1], bstart[c + 2])
-  float4* blk = nullptr;
-  uint32_t* bstart = nullptr;     // ncells + 1 prefix offsets into blk
-  int64_t nblk = 0;
-  int device = 0;
-  // map maintenance (slio_map_add_points / slio_map_delete_boxes /
-  // slio_map_incremental): deletions are flags on pts positions, additions
-  // wait in add4 (id order) until the next rebuild of the index (map_refresh,
-  // before the next search pass or download).  Point ids: 0..n-1 for the
-  // upload, then the next ids for every surviving added point.
-  uint8_t* keep = nullptr;        // n: 0 = deleted since the last build
-  float4* add4 = nullptr;         // x, y, z, bits(id)
-  uint8_t* akeep = nullptr;
-  int64_t nadd = 0, add_cap = 0;
-  uint32_t next_id = 0;
-  // stored points deleted since the coarse boxes were last made tight (merge
-  // rebuilds only widen them): past n / kCoarseRetighten they are rebuilt
-  int64_t del_loose = 0;
-  std::atomic<uint64_t> version{1};  // bumped by every rebuild (positions change)
-  std::atomic<bool> dirty{false};
-  // block rows of a rebuilt map are built once it has been searched
-  // kBlkAfterPasses times unchanged (a map changed every scan goes without:
-  // they cost ~1 ms per rebuild and save ~5 us per search pass)
-  std::atomic<bool> blk_deferred{false};
-  int stable_passes = 0;
-  // Sharing (slio_map_share).  Changes -- edits, rebuilds, block rows --
-  // hold mu exclusively; passes and reads hold it shared from reading the
-  // views through their launches.  Streams: a change first orders its stream
-  // after everything the other users have enqueued (they may still be
-  // reading what it overwrites: map_write_begin), then records `ready` and
-  // bumps `epoch`; a reader whose stream has not yet waited for the current
-  // epoch waits for `ready` (map_read_sync).
-  std::shared_mutex mu;
-  std::vector<Ctx*> users;  // handles holding this map
-  hipEvent_t ready = nullptr;
-  uint64_t epoch = 0;
-  bool broken = false;  // an index rebuild failed part-way: unusable until a new upload
-  int64_t sequential_calls = 0;  // Add_Points calls that took k_ds_sequential (diagnostic)
-  float cell0 = 1.0f;             // requested grid cell and cell budget (slio_params)
-  int64_t max_cells = 0;
-  // device allocations kept across index rebuilds (capacity in bytes): a
-  // rebuild per scan must not pay hipMalloc / hipFree of ~GB tables
-  struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-  };
-  Buf b_pts, b_keep, b_start, b_clo, b_chi, b_bstart, b_blk, b_tmp[8], b_ref[6], b_add[8], b_start2, b_keep2;
-  static hipError_t take(Buf& b, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 16);
-    if (bytes <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    size_t want = bytes + bytes / 4;  // headroom: the map grows scan by scan
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e) {
-      (void)hipGetLastError();
-      want = bytes;
-      e = hipMalloc(&b.p, want);
-    }
-    if (!e) b.cap = want;
-    return e;
-  }
-  void free_index() {  // the views only; allocations stay for the next build
-    pts = nullptr;
-    start = nullptr;
-    blk = nullptr;
-    bstart = nullptr;
-    clo = nullptr;
-    chi = nullptr;
-    keep = nullptr;
-    n = ncells = nccells = nblk = 0;
-  }
-  ~MapDev() {
-    if (ready) (void)hipEventDestroy(ready);
-    for (Buf* b : {&b_pts, &b_keep, &b_start, &b_clo, &b_chi, &b_bstart, &b_blk, &b_start2, &b_keep2})
-      if (b->p) (void)hipFree(b->p);
-    for (Buf& b : b_tmp)
-      if (b.p) (void)hipFree(b.p);
-    for (Buf& b : b_ref)
-      if (b.p) (void)hipFree(b.p);
-    for (Buf& b : b_add)
-      if (b.p) (void)hipFree(b.p);
-    if (add4) (void)hipFree(add4);
-    if (akeep) (void)hipFree(akeep);
-  }
-};
-
-// trivially-copyable kernel argument view of a MapDev
-struct MapView {
-  GridGeom g;
-  int64_t n;
-  const float4* pts;
-  const uint32_t* start;
-  const float4* blk;       // null: the 3x3x3 block is scanned as 9 runs of pts
-  const uint32_t* bstart;
-  int64_t nblk;
-  int64_t ncells;
-  CoarseView cl;
-};
-
 #ifdef SLIO_BOUNDS_CHECK
 __constant__ int64_t c_dbg_npts, c_dbg_ncells;  // set by slio_map_upload
 // diagnostic build only: report and neutralise an out-of-range index
@@ -300,12 +153,6 @@ __constant__ int64_t c_dbg_npts, c_dbg_ncells;  // set by slio_map_upload
   do {                            \
   } while (0)
 #endif
-
-__device__ __host__ __forceinline__ int cell_coord(float p, float o, float inv_h) {
-  float t = floorf((p - o) * inv_h);
-  t = fminf(fmaxf(t, -1.0e8f), 1.0e8f);
-  return (int)t;
-}
 
 // per-cell counts of SORTED keys (cell = key >> shift): one atomic per run of
 // equal cells inside a wavefront (sorted keys put up to 64 lanes on one
@@ -583,15 +430,6 @@ __global__ void k_coarse_extend(const float4* __restrict__ adds, const uint8_t* 
 }
 
 // ---------------------------------------------------------------- math helpers
-struct PoseDev {
-  double rq[4], pos[3], lq[4], tli[3];  // quaternions (w, x, y, z)
-  double R[9];                          // rot.matrix(), row-major
-  double RL[9];                         // offset_R_L_I.matrix(), row-major
-};
-
-static_assert(sizeof(PoseDev) == 32 * sizeof(double), "PoseDev: 32 doubles (IkfCtl::pose)");
-static_assert(sizeof(IkfCtl::pose[0]) == sizeof(PoseDev), "IkfCtl::pose slots hold a PoseDev");
-
 // double e of pose_from_state(x) (the PoseDev layout), for the filter step
 // to store the next pass's pose: the pass kernels then read it with scalar
 // loads (pose_of_ctl) instead of forming the two matrices in vector
@@ -741,33 +579,7 @@ __device__ __forceinline__ bool residual_gate(const float (&abcd)[4], float wx, 
 }
 
 // ---------------------------------------------------------------- top-5
-// Sorted top-5 list of 64-bit keys (float bits(squared distance) << 32) |
-// position in the cell-sorted map: one u64 compare orders by distance, then
-// by map position (squared distances are >= +0, whose bit patterns sort like
-// the values).  The map index is read back from the point (float4.w) only for
-// the five winners.
-struct Top5 {
-  uint64_t k[5];
-};
-
-__device__ __forceinline__ void top5_clear(Top5& t) {
-#pragma unroll
-  for (int j = 0; j < 5; ++j) t.k[j] = kInfKey;
-}
-
-// Branch-free insertion: slot j takes k[j-1] if key < k[j-1], key if
-// k[j-1] <= key < k[j], else keeps k[j]; a key >= k[4] changes nothing.  All
-// five slots update in parallel (no serial compare-swap chain, no divergent
-// branch: across a wavefront some lane nearly always inserts).
-__device__ __forceinline__ void top5_insert(Top5& t, uint64_t key) {
-  bool c[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) c[j] = key < t.k[j];
-#pragma unroll
-  for (int j = 4; j > 0; --j) t.k[j] = c[j - 1] ? t.k[j - 1] : (c[j] ? key : t.k[j]);
-  t.k[0] = c[0] ? key : t.k[0];
-}
-
+// (Top5, top5_insert, the DPP merge of Top5 lists: slio_search.hpp)
 // A sorted top-5 list with the smallest squared distance it has DROPPED (an
 // evicted entry or a rejected key): after a scan, every scanned candidate
 // outside the list lies at >= m (the 6th distance of the scanned set).  The
@@ -813,22 +625,6 @@ __device__ __forceinline__ void consider(Top5& t, const float4 c, uint32_t pos, 
   top5_insert(t, ((uint64_t)__float_as_uint(d) << 32) | (uint64_t)pos);
 }
 
-// 64-bit lane exchange by DPP (a VALU operand modifier, no LDS round trip)
-template <int CTRL>
-__device__ __forceinline__ uint64_t dpp64(uint64_t v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
-  return ((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo;
-}
-
-template <int CTRL>
-__device__ __forceinline__ void merge_round_dpp(Top5& t) {
-  uint64_t ok[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) ok[j] = dpp64<CTRL>(t.k[j]);
-#pragma unroll
-  for (int j = 0; j < 5; ++j) top5_insert(t, ok[j]);
-}
 template <int CTRL>
 __device__ __forceinline__ void merge_round_dpp(Top5M& a) {
   uint64_t ok[5];
@@ -855,27 +651,6 @@ __device__ __forceinline__ void merge_round_dpp(Top6M& a) {
 // list and the union's dropped minimum)
 __device__ __forceinline__ void group_merge2(Top5M& a) { merge_round_dpp<0xB1>(a); }
 __device__ __forceinline__ void group_merge2(Top6M& a) { merge_round_dpp<0xB1>(a); }
-
-// butterfly merge of the LPQ per-lane lists of a query group (lanes of a
-// group are consecutive and aligned, and all active or all inactive).  Up to
-// 16 lanes by DPP: quad_perm [1,0,3,2] and [2,3,0,1] merge each quad, then
-// row_half_mirror (lane i <-> 7 - i) pairs the two quads of 8 lanes and
-// row_mirror (i <-> 15 - i) the two halves of 16; wider groups by ds_bpermute.
-template <int LPQ>
-__device__ __forceinline__ void group_merge(Top5& t) {
-  if (LPQ >= 2) merge_round_dpp<0xB1>(t);
-  if (LPQ >= 4) merge_round_dpp<0x4E>(t);
-  if (LPQ >= 8) merge_round_dpp<0x141>(t);
-  if (LPQ >= 16) merge_round_dpp<0x140>(t);
-#pragma unroll
-  for (int m = 16; m < LPQ; m <<= 1) {
-    uint64_t ok[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) ok[j] = __shfl_xor(t.k[j], m);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) top5_insert(t, ok[j]);
-  }
-}
 
 // The same merge as a rolled loop over ds_bpermute rounds: for cold code
 // (the refinement path runs in few workgroups, so its instructions are
@@ -1236,39 +1011,7 @@ __device__ __forceinline__ void scan_cube(const float4* __restrict__ pts, const 
   }
 }
 
-// Exactness bound: every map point outside cube [c-r, c+r] lies at least this
-// far from q (minus float slack); +inf when the cube covers the grid.
-__device__ __forceinline__ float outside_bound(const GridGeom& g, int cx, int cy, int cz, int r,
-                                               float qx, float qy, float qz, bool& covers) {
-  const float INF = __int_as_float(0x7f800000);
-  float b = INF;
-  covers = true;
-  auto axis = [&](int c, int d, float o, float q) {
-    if (c - r > 0) {
-      covers = false;
-      const float face = o + (float)(c - r) * g.h + g.tol;
-      b = fminf(b, q - face);
-    }
-    if (c + r < d - 1) {
-      covers = false;
-      const float face = o + (float)(c + r + 1) * g.h - g.tol;
-      b = fminf(b, face - q);
-    }
-  };
-  axis(cx, g.dx, g.ox, qx);
-  axis(cy, g.dy, g.oy, qy);
-  axis(cz, g.dz, g.oz, qz);
-  return b;
-}
-
 // ---------------------------------------------------------------- kernels
-struct ScanDev {
-  const float* bx;
-  const float* by;
-  const float* bz;
-  int64_t n;
-};
-
 struct PassOut {
   int32_t* nbr_idx;  // n * 5  (map point ids)
   uint32_t* nbr_pos; // n * 5  (positions in the cell-sorted pts, for map_incremental)
@@ -1326,8 +1069,8 @@ constexpr uint32_t kPlaneRejected = 0x7fc00e57u;
 // A query the fine grid cannot finish (its 5th neighbour lies beyond the
 // 5x5x5 fine cube, or its cell lies outside the grid) is DEFERRED to the end
 // of the kNN phase of its workgroup, where the workgroup's wavefronts answer
-// the chunk's deferred queries one per wavefront (far_search, all 64 lanes
-// on one query).  Such queries are rare (returns with no map support within
+// the chunk's deferred queries one per wavefront (far_search in
+// slio_search.hpp, all 64 lanes on one query).  Such queries are rare (returns with no map support within
 // a few metres, e.g. a scan taken from inside a building or far outside the
 // map); handled inline on their own 2 lanes they serialised the wavefront
 // that held them.  (An earlier global work queue spread them over the chip
@@ -1336,223 +1079,11 @@ constexpr uint32_t kPlaneRejected = 0x7fc00e57u;
 typedef __attribute__((address_space(1))) uint32_t gu32;
 
 __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 __device__ __forceinline__ void st_sc1_u32(uint32_t* p, uint32_t v) {
   __hip_atomic_store((gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ uint32_t ld_sc1_u32(const uint32_t* p) {
   return __hip_atomic_load((gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// exclusive prefix sum over the wavefront's 64 lanes; total to every lane
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t& total) {
-  const int lane = threadIdx.x & 63;
-  uint32_t s = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(s, d, 64);
-    if (lane >= d) s += o;
-  }
-  total = __shfl(s, 63, 64);
-  return s - v;
-}
-
-// The exact 5-NN of one query by a whole wavefront on the coarse level:
-// Chebyshev rings R = 0, 1, ... of coarse cells around the query's (clamped)
-// cell; a cell is scanned unless its tight box lies farther than the bound
-// (the 5th distance found so far, or bound0: the 5th distance of 5 real map
-// points, or +inf).  The candidate cells of a batch of 64 ring positions are
-// expanded, four at a time, into their 16 runs of the fine pts (one per fine
-// (y, z) row), flattened into one list (lane prefix sums in LDS, a 6-step
-// binary search per candidate) and swept with U loads in flight per lane.  The search ends
-// when every unscanned cell lies beyond the 5th distance: the bound over the
-// six slabs outside the ring's cube is per-axis exact (face distance on the
-// slab's axis, distance to the grid's range on the other two).  Keys carry
-// the fine pts position, so results equal the fine grid's.  Returns the list
-// in every lane.  KNN = 1 (the loop-closure ICP pass, k_icp_pass) bounds and
-// ends the search by the nearest distance instead of the 5th: entry 0 is then
-// the exact nearest key, the same one a KNN = 5 search puts there.
-template <int U, int KNN = 5>
-__device__ __forceinline__ void far_search(const MapView& map, float qx, float qy, float qz,
-                                        float bound, uint32_t* __restrict__ pre,
-                                        uint32_t* __restrict__ beg, Top5& t) {
-  const int lane = threadIdx.x & 63;
-  const CoarseView& cv = map.cl;
-  const GridGeom g = cv.g, fg = map.g;
-  const float INF = __int_as_float(0x7f800000);
-  top5_clear(t);
-  bool full = false;
-  float d5 = INF;
-  const int CX = min(max(cell_coord(qx, g.ox, g.inv_h), 0), g.dx - 1);
-  const int CY = min(max(cell_coord(qy, g.oy, g.inv_h), 0), g.dy - 1);
-  const int CZ = min(max(cell_coord(qz, g.oz, g.inv_h), 0), g.dz - 1);
-  // distance of q to the grid's range on each axis (every map point lies in it)
-  auto range_gap = [&](float q, float o, int d) {
-    const float lo = o - g.tol, hi = o + (float)d * g.h + g.tol;
-    return fmaxf(fmaxf(lo - q, q - hi), 0.0f);
-  };
-  const float ax = range_gap(qx, g.ox, g.dx), ay = range_gap(qy, g.oy, g.dy),
-              az = range_gap(qz, g.oz, g.dz);
-  // conservative squared gap from q to the cells [a0, a1] of one axis
-  auto span_gap = [&](float q, float o, int a0, int a1) {
-    const float lo = o + (float)a0 * g.h - g.tol, hi = o + (float)(a1 + 1) * g.h + g.tol;
-    const float d = fmaxf(fmaxf(lo - q, q - hi), 0.0f);
-    return d * d;
-  };
-  for (int R = 0;; ++R) {
-    const int x0 = max(CX - R, 0), x1 = min(CX + R, g.dx - 1);
-    const int y0 = max(CY - R, 0), y1 = min(CY + R, g.dy - 1);
-    const int z0 = max(CZ - R, 0), z1 = min(CZ + R, g.dz - 1);
-    // the ring's shell (cube R minus cube R-1, clipped to the grid) as up to
-    // six face rectangles: x faces over the full (y, z) span, y faces over
-    // the inner x span, z faces over the inner x and y spans.  A face whose
-    // box lies beyond the bound is skipped whole (its cells would all fail
-    // the per-cell test below).
-    const int xi0 = max(CX - R + 1, 0), xi1 = min(CX + R - 1, g.dx - 1);
-    const int yi0 = max(CY - R + 1, 0), yi1 = min(CY + R - 1, g.dy - 1);
-    const float lim_f = fminf(bound, d5);
-    int fa[6], fna[6], fb[6], fv[6], cum[7];
-    cum[0] = 0;
-#pragma unroll
-    for (int f = 0; f < 6; ++f) {
-      const int fax = f >> 1;                              // fixed axis
-      const int C = fax == 0 ? CX : fax == 1 ? CY : CZ;
-      const int D = fax == 0 ? g.dx : fax == 1 ? g.dy : g.dz;
-      const int v = (f & 1) ? C + R : C - R;
-      const bool ok = (f == 0 || R > 0) && v >= 0 && v < D;
-      int a0, a1, b0, b1;
-      float gsum;
-      if (fax == 0) {
-        a0 = y0; a1 = y1; b0 = z0; b1 = z1;
-        gsum = (span_gap(qx, g.ox, v, v) + span_gap(qy, g.oy, a0, a1)) + span_gap(qz, g.oz, b0, b1);
-      } else if (fax == 1) {
-        a0 = xi0; a1 = xi1; b0 = z0; b1 = z1;
-        gsum = (span_gap(qx, g.ox, a0, a1) + span_gap(qy, g.oy, v, v)) + span_gap(qz, g.oz, b0, b1);
-      } else {
-        a0 = xi0; a1 = xi1; b0 = yi0; b1 = yi1;
-        gsum = (span_gap(qx, g.ox, a0, a1) + span_gap(qy, g.oy, b0, b1)) + span_gap(qz, g.oz, v, v);
-      }
-      const bool live_f = ok && a0 <= a1 && b0 <= b1 && !(gsum * 0.99999f > lim_f);
-      fa[f] = a0;
-      fb[f] = b0;
-      fv[f] = v;
-      fna[f] = live_f ? a1 - a0 + 1 : 0;
-      cum[f + 1] = cum[f] + (live_f ? (a1 - a0 + 1) * (b1 - b0 + 1) : 0);
-    }
-    const int total = cum[6];
-    for (int base = 0; base < total; base += 64) {
-      const int p = base + lane;
-      bool pass = false;
-      int ccx = 0, ccy = 0, ccz = 0;
-      if (p < total) {
-        int f = 0;
-#pragma unroll
-        for (int j = 1; j < 6; ++j) f = p >= cum[j] ? j : f;
-        int A = 0, B = 0, V = 0, NA = 1;
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-          if (f == j) {
-            A = fa[j];
-            B = fb[j];
-            V = fv[j];
-            NA = fna[j];
-          }
-        const int l = p - (f == 0 ? 0 : f == 1 ? cum[1] : f == 2 ? cum[2] : f == 3 ? cum[3] : f == 4 ? cum[4] : cum[5]);
-        const int ua = A + l % NA, ub = B + l / NA;
-        const int fax = f >> 1;
-        ccx = fax == 0 ? V : ua;
-        ccy = fax == 0 ? ua : fax == 1 ? V : ub;
-        ccz = fax == 2 ? V : ub;
-        const uint32_t c = ((uint32_t)ccz * (uint32_t)g.dy + (uint32_t)ccy) * (uint32_t)g.dx + (uint32_t)ccx;
-        const float4 lo = cv.lo[c];
-        if (__float_as_uint(lo.w)) {
-          const float4 hi = cv.hi[c];
-          const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.0f);
-          const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.0f);
-          const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.0f);
-          const float gd = (gx * gx + gy * gy) + gz * gz;
-          pass = !(gd > fminf(bound, d5));  // a point at exactly d5 may still win on position
-        }
-      }
-      // the passing coarse cells, four at a time: lane l reads the bounds of
-      // fine row (l & 15) of passing cell (l >> 4), one run of the fine pts
-      uint64_t pm = __ballot(pass);
-      const int gi = lane >> 4, sl = lane & 15;
-      while (pm) {
-        uint64_t bm = pm;
-        for (int q = 0; q < gi && bm; ++q) bm &= bm - 1;  // the gi-th passing cell
-        const bool act = bm != 0;
-        const int src = act ? __ffsll((unsigned long long)bm) - 1 : 0;
-        // (every lane shuffles: a cross-lane read inside a condition would
-        // read lanes the condition turned off)
-        const int x = __shfl(ccx, src, 64), y = __shfl(ccy, src, 64), z = __shfl(ccz, src, 64);
-        for (int q = 0; q < 4 && pm; ++q) pm &= pm - 1;
-        uint32_t s = 0, k = 0;
-        const int fy = 4 * y + (sl & 3), fz = 4 * z + (sl >> 2);
-        if (act && fy < fg.dy && fz < fg.dz) {
-          const int64_t rb = ((int64_t)fz * fg.dy + fy) * fg.dx;
-          s = map.start[rb + 4 * x];
-          k = map.start[rb + min(4 * x + 4, fg.dx)] - s;
-        }
-        if (!__any(k != 0)) continue;
-        uint32_t tot;
-        const uint32_t ex = wave_excl_scan(k, tot);
-        pre[lane] = ex;
-        beg[lane] = s;
-        wave_fence();
-        for (uint32_t f0 = 0; f0 < tot; f0 += 64 * U) {
-          uint32_t a[U];
-          float4 c[U];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const uint32_t f = min(f0 + (uint32_t)(u * 64 + lane), tot - 1);
-            int j = 0;
-#pragma unroll
-            for (int st = 32; st > 0; st >>= 1)
-              if (pre[j + st] <= f) j += st;
-            a[u] = beg[j] + (f - pre[j]);
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) c[u] = map.pts[a[u]];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const float ddx = qx - c[u].x, ddy = qy - c[u].y, ddz = qz - c[u].z;
-            const float d = (ddx * ddx + ddy * ddy) + ddz * ddz;  // calc_dist, ikd_Tree.cpp:1539-1544
-            const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint64_t)a[u];
-            top5_insert(t, (f0 + (uint32_t)(u * 64 + lane) < tot) ? key : kInfKey);
-          }
-        }
-        group_merge<64>(t);  // every lane: the merged list
-        full = t.k[KNN - 1] != kInfKey;
-        if (full) d5 = __uint_as_float((uint32_t)(t.k[KNN - 1] >> 32));
-        if (lane != 0) top5_clear(t);  // lane 0 keeps it
-        wave_fence();                  // pre / beg are rewritten by the next batch
-      }
-    }
-    // lower bound of the squared distance to every cell outside this cube
-    float lb = INF;
-    bool covers = true;
-    auto slab = [&](bool open, float face_gap, float o1, float o2) {
-      if (!open) return;
-      covers = false;
-      const float f = fmaxf(face_gap, 0.0f);
-      lb = fminf(lb, (f * f + o1 * o1) + o2 * o2);
-    };
-    slab(x0 > 0, qx - (g.ox + (float)x0 * g.h + g.tol), ay, az);
-    slab(x1 < g.dx - 1, (g.ox + (float)(x1 + 1) * g.h - g.tol) - qx, ay, az);
-    slab(y0 > 0, qy - (g.oy + (float)y0 * g.h + g.tol), ax, az);
-    slab(y1 < g.dy - 1, (g.oy + (float)(y1 + 1) * g.h - g.tol) - qy, ax, az);
-    slab(z0 > 0, qz - (g.oz + (float)z0 * g.h + g.tol), ax, ay);
-    slab(z1 < g.dz - 1, (g.oz + (float)(z1 + 1) * g.h - g.tol) - qz, ax, ay);
-    if (covers || (full && d5 < lb * 0.99999f)) break;
-    if (R > g.dx + g.dy + g.dz) break;  // unreachable: the cube covers the grid long before
-  }
-#pragma unroll
-  for (int j = 0; j < 5; ++j) t.k[j] = __shfl(t.k[j], 0, 64);
 }
 
 __device__ __forceinline__ int64_t xcd_chunk(int64_t c_begin, int64_t nblk) {
@@ -3725,117 +3256,6 @@ __global__ __launch_bounds__(kSolveThreads) void k_ikf_solve(IkfCtl* ctl, const 
 }
 
 // ---------------------------------------------------------------- context
-struct Ctx {
-  slio_params prm{};
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  std::shared_ptr<MapDev> map;
-  // scan
-  int64_t n = 0;
-  float* bx = nullptr;
-  float* by = nullptr;
-  float* bz = nullptr;
-  int32_t* nbr_idx = nullptr;
-  uint32_t* nbr_pos = nullptr;
-  PoseDev* nbr_pose = nullptr;  // pose of the last search pass (device)
-  bool nbr_lazy = false;        // nbr_idx / nbr_sqd not yet derived from nbr_pos
-  bool nbr_stale = false;       // ... and no longer derivable: another handle rebuilt the shared map
-  uint64_t search_version = 0;  // map version the last search pass ran on
-  uint64_t seen_epoch = 0;      // the map's last change this handle's stream is ordered after
-  hipEvent_t map_ev = nullptr;  // recorded on this stream by another user's map change
-  float* wbx = nullptr;  // scan-to-map: the scan in the map frame
-  float* wby = nullptr;
-  float* wbz = nullptr;
-  int s2m_kind = -1;
-  float* nbr_sqd = nullptr;
-  float4* plane = nullptr;
-  uint8_t* sel = nullptr;
-  float* resid = nullptr;
-  double* chunk_part = nullptr;
-  uint32_t* chunk_cost = nullptr;  // per chunk of the last search pass (chunk_order)
-  // kNN certificates of the device-resident update (k_search_pass): per point
-  // query + bound (the 5 positions are nbr_pos); per chunk the update epoch
-  float4* kq = nullptr;
-  uint32_t* k6 = nullptr;
-  uint32_t* kepoch = nullptr;
-  uint32_t kc_next = 0;       // last epoch handed out
-  uint32_t kc_epoch = 0;      // the running update's (0: certificates off)
-  uint64_t kc_version = 0;    // map version of the update's first pass
-  bool kc_stats = false;      // count certified / searched queries (slio_debug_knn_cert): two
-                              // same-address atomics per workgroup, off the product path
-  uint32_t* chunk_perm = nullptr;  // search order for the next device-resident pass
-  int cus_per_xcd = 0;             // CUs per XCD (0: chunk_order off)
-  // far queue (deferred queries, see far_search)
-  double* d_super = nullptr;
-  double* d_super_own = nullptr;
-  double* d_seg = nullptr;    // the pass's 64 segment rows (k_super_sums hand-off)
-  void* comm = nullptr;        // RCCL communicator of the rank group (slio_comm_init / slio_create_group)
-  int group_reduce = 0;        // slio_create_group: 1 RCCL communicator, 2 in-device reduce (k_group_reduce)
-  hipEvent_t grp_ev = nullptr; // in-device reduce: end of this rank's pass / of the reduce (rank 0)
-  double* gsup = nullptr;      // fused group pass (rank 0): the group's 8 super rows
-  uint32_t* garrive = nullptr; // ... and the ranks' arrival counter
-  int32_t group_seq = 0;       // fused group pass: the running update's sequence number (0: none)
-  int32_t upd_seq = 0;         // (rank 0) last sequence number handed out
-  uint32_t* count = nullptr;  // [0] k_super_sums arrival counter, [4..5] far-queue head / tail,
-  MapDev::Buf inc[7];         // map_incremental temporaries, kept across scans
-                              // (zero between launches)
-  MapDev::Buf pre[16];        // undistortion / VoxelGrid temporaries, kept across scans
-                              // (per-call hipMalloc + hipFree cost more than the kernels)
-  // LIO-SAM keyframe store (slio_s2m_kf_*): one growing SoA arena, keyframe k
-  // at [kf_off[k], kf_off[k] + kf_len[k])
-  float* kfx = nullptr;
-  float* kfy = nullptr;
-  float* kfz = nullptr;
-  int64_t kf_used = 0, kf_cap = 0;
-  std::vector<int64_t> kf_off, kf_len;
-  MapDev::Buf kfb[3];         // map assembly: the concatenation (SoA), the segment table,
-                              // build_index's input; kept across scans
-  hipEvent_t kf_ev = nullptr; // orders another handle's assembly after this store's pushes
-                              // (slio_s2m_loop_cloud)
-  // loop-closure ICP (slio_icp_correspond): the working cloud (SoA), the last
-  // pass's map id and squared distance per working point, the workgroup partials
-  MapDev::Buf icp[4];
-  int64_t icp_n = -1;         // working points (-1: no pass yet)
-  int64_t icp_far = 0;        // queries the last pass sent down the far path
-  IkfCtl* ctl = nullptr;   // device-resident update state (HBM)
-  IkfCtl* h_ctl = nullptr;  // mapped, coherent host block: update input and output
-  IkfCtl* d_hctl = nullptr; // its device view
-  hipEvent_t done_ev = nullptr;  // end of a device-resident update (polled)
-  double* h_super = nullptr;  // pinned
-  bool searched = false;
-  // profiling: event pairs pending per kind, accumulated time
-  bool prof = false;
-  int prof_mask = 0;  // bit k: time kernel kind k
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[3];
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double prof_ms[3] = {0, 0, 0};
-  int64_t prof_n[3] = {0, 0, 0};
-  // diagnostic switches of the update path, read from the environment once
-  // per handle (slio_create, slio_debug_reload_switches): no getenv on the
-  // host turnaround between updates
-  struct Switches {
-    bool no_fuse = false;     // SLIO_NO_FUSE: two launches per pass
-    bool no_fuse0 = false;    // SLIO_NO_FUSE0: two launches for the first pass
-    bool no_mfma = false;     // SLIO_NO_MFMA: VALU chunk products
-    bool event_wait = false;  // SLIO_EVENT_WAIT: wait on a completion event
-    bool no_kc = false;       // SLIO_NO_KNN_CERT: every pass searches in full
-    bool persist = false;     // SLIO_PERSIST: one persistent launch per update (k_update_persist)
-  } sw;
-  // persistent update (k_update_persist): the flag replicas, the CU count and
-  // the workgroups the device holds at once (-1: not yet queried)
-  uint64_t* goflag = nullptr;
-  int ncu = 0;
-  int64_t persist_cap = -1;
-  int last_path = 0;  // the last device-resident update: 1 persistent launch, 0 a launch per pass
-  bool dev_counted = false;  // counted in dev_users (slio_create succeeded)
-  uint64_t wait_ticks = 0;  // device-side waits give up after this many 100 MHz ticks (0: 1 s;
-                            // slio_debug_wait_limit)
-  // host clock stamps (CLOCK_MONOTONIC ns) of the last device-resident update
-  // (slio_debug_host_stamps)
-  bool hstamp = false;
-  int64_t hst[8] = {};
-};
-
 int dev_users(int device, int delta) {
   static std::atomic<int> users[256];
   if (device < 0 || device >= 256) return 0;
@@ -3912,7 +3332,7 @@ static int map_write_end(Ctx& c) {
   c.seen_epoch = ++m.epoch;
   return SLIO_OK;
 }
-static int map_read_sync(Ctx& c) {
+int map_read_sync(Ctx& c) {
   MapDev& m = *c.map;
   if (c.seen_epoch != m.epoch) {
     if (m.ready) SLIO_HIP(hipStreamWaitEvent(c.stream, m.ready, 0));
@@ -3950,7 +3370,7 @@ static int init_constants() {
   return SLIO_OK;
 }
 
-static PoseDev make_pose(const slio_pose* x) {
+PoseDev make_pose(const slio_pose* x) {
   PoseDev P;
   for (int j = 0; j < 4; ++j) {
     P.rq[j] = x->rot[j];
@@ -4059,16 +3479,7 @@ static hipError_t spin_sync(hipStream_t st) {
   return e;
 }
 
-// Small device -> host reads (scan totals, counters, boxes) through a pinned
-// staging buffer of the calling thread, then one polled wait: a copy into
-// pageable host memory waits inside the runtime, and a blocking stream
-// synchronisation wakes ~10-20 us late.
-struct Rb {
-  void* dst;
-  const void* src;
-  size_t n;
-};
-static hipError_t readback(hipStream_t st, const Rb* rb, int k) {
+hipError_t readback(hipStream_t st, const Rb* rb, int k) {
   thread_local uint8_t* pin = nullptr;
   thread_local size_t cap = 0;
   size_t tot = 0;
@@ -4163,15 +3574,12 @@ struct SolveArgs {
 };
 
 static void enqueue_super(Ctx& c, IkfCtl* ctl, const SolveArgs* sa);
-static int map_refresh(Ctx& c, bool adds_only = false);
 static int map_refresh_locked(Ctx& c, bool adds_only);
 static int nbr_settle_shared(Ctx& c);
 static int build_blk(MapDev& m, hipStream_t st, const char* who);
 
-static int enqueue_pass(Ctx& c, const PoseDev* Parg, IkfCtl* ctl, int which,
-                        int extrinsic_est, const SolveArgs* sa = nullptr,
-                        bool with_super = true, bool knn_only = false, const ScanDev* sd = nullptr,
-                        const FuseArgs* fuse = nullptr, int persist = 0) {
+int enqueue_pass(Ctx& c, const PoseDev* Parg, IkfCtl* ctl, int which, int extrinsic_est, const SolveArgs* sa,
+                 bool with_super, bool knn_only, const ScanDev* sd, const FuseArgs* fuse, int persist) {
   if (!c.map) {
     set_error("slio pass: no map uploaded");
     return SLIO_ESTATE;
@@ -4393,23 +3801,10 @@ static void enqueue_super(Ctx& c, IkfCtl* ctl, const SolveArgs* sa) {
 
 using namespace slio;
 
-struct slio_ctx {
-  Ctx c;
-};
-
 namespace slio {
 void* internal_stream(slio_handle h) { return h ? (void*)h->c.stream : nullptr; }
 
 }  // namespace slio
-
-#define SLIO_CHECK_H(h)                                  \
-  do {                                                   \
-    if (!(h)) {                                          \
-      set_error("null handle");                          \
-      return SLIO_EINVAL;                                \
-    }                                                    \
-    SLIO_HIP(hipSetDevice((h)->c.prm.device));           \
-  } while (0)
 
 extern "C" {
 
@@ -4738,7 +4133,7 @@ __global__ void k_widen_flags(const uint8_t* __restrict__ k, int64_t n, uint32_t
   if (i < n) f[i] = k[i] ? 1u : 0u;
 }
 
-static int grid_blocks(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
+int grid_blocks(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
 
 // ---- survivor ranks straight from the keep bytes (the merge rebuild's
 // exclusive prefix count of the stored points): per-tile counts, one
@@ -5077,7 +4472,7 @@ static int build_index(MapDev& m, const float4* in, int64_t n, const float mn[3]
   return rc;
 }
 
-static int ensure_scan_buffers(Ctx& c) {
+int ensure_scan_buffers(Ctx& c) {
   if (!c.bx) {
     const int64_t cap = c.prm.max_points;
     const int64_t capc = num_chunks(cap) + 1;
@@ -5941,37 +5336,9 @@ k_vg_centroids4(const float* __restrict__ x, const float* __restrict__ y, const 
 // concatenation, in ONE launch.  The keyframes live in the handles' SoA
 // arenas; seg[s] describes the s-th NON-EMPTY selected entry: its first
 // position in the concatenation, its first point in its arena and the
-// float affine of its pose (pcl::getTransformation, host).
-struct KfSeg {
-  const float *x, *y, *z;  // the keyframe's first point in its store's arena (the loop-closure
-                           // cloud reads two stores in one launch: slio_s2m_loop_cloud)
-  uint32_t off;            // concatenation position of the entry's first point
-  uint32_t pad;
-  float m[12];
-};
-constexpr int kKfTile = 256;
-
-// LeGO-LOAM's pointAssociateToMap / transformPointCloud
-// (LeGO-LOAM/src/mapOptmization.cpp:578-607, :624-652): not an affine but
-// three successive float rotations -- yaw about z, roll about x, pitch about
-// y -- then the translation, with the six cached float sines and cosines
-// (:562-576, :609-622; the trig in double, rounded to float, on the host)
-struct LegoRot {
-  float cr, sr, cp, sp, cy, sy, tx, ty, tz;
-};
-__device__ __forceinline__ void lego_to_map(const LegoRot& T, float x, float y, float z, float& ox, float& oy,
-                                            float& oz) {
-  const float x1 = T.cy * x - T.sy * y;
-  const float y1 = T.sy * x + T.cy * y;
-  const float z1 = z;
-  const float x2 = x1;
-  const float y2 = T.cr * y1 - T.sr * z1;
-  const float z2 = T.sr * y1 + T.cr * z1;
-  ox = T.cp * x2 + T.sp * z2 + T.tx;
-  oy = y2 + T.ty;
-  oz = -T.sp * x2 + T.cp * z2 + T.tz;
-}
-
+// float affine of its pose (pcl::getTransformation, host).  (KfSeg, LegoRot
+// and lego_to_map: slio_device.hpp; the table is made in slio_mapopt.hip.)
+//
 // Each workgroup takes tiles of kKfTile consecutive concatenation positions;
 // the segments a tile touches (at most kKfTile: none is empty) are staged in
 // LDS and each thread finds its own by bisection there.  World point =
@@ -6670,7 +6037,7 @@ static int merge_rebuild(MapDev& m, hipStream_t st, bool* handled) {
 // Rebuild the index from the surviving points and the pending additions
 // (when the map changed since the last build).  adds_only: only when points
 // were added (deletions alone are honoured through the keep flags).
-static int map_refresh(Ctx& c, bool adds_only) {
+int map_refresh(Ctx& c, bool adds_only) {
   if (!c.map || !c.map->dirty) return SLIO_OK;
   std::unique_lock<std::shared_mutex> lk(c.map->mu);
   if (!c.map->dirty) return SLIO_OK;  // another user rebuilt it meanwhile
@@ -7354,8 +6721,8 @@ static int vg_enqueue(Ctx& c, const VgWork& w, const float* dx_, const float* dy
 }
 
 // downSizeFilterSurf of n device points (dx_, dy_, dz_) into the handle's scan
-static int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float* dz_, int64_t n, float leaf,
-                        int64_t* n_down) {
+int slio::voxel_device(Ctx& c, const float* dx_, const float* dy_, const float* dz_, int64_t n, float leaf,
+                       int64_t* n_down) {
   hipStream_t st = c.stream;
   int rc = nbr_settle_shared(c);  // the scan it was searched with is replaced
   if (rc) return rc;
@@ -7421,790 +6788,6 @@ static int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float*
   }
   return rc;
 }
-
-// ---------------------------------------------------------------- LIO-SAM scan-to-map
-// mapOptmization.cpp cornerOptimization (:1303-1432), surfOptimization
-// (:1438-1515) and the rows / normal equations of LMOptimization
-// (:1552-1626) on the device; the 6x6 solve stays on the host
-// (slio_s2m_lm_step).  One handle per feature class: its map is
-// laserCloud{Corner,Surf}FromMapDS, its scan laserCloud{Corner,Surf}LastDS.
-
-// pointAssociateToMap (:359-373) with the float affine of
-// pcl::getTransformation(transformTobeMapped)
-struct Aff12 {
-  float m[12];
-};
-__global__ void k_s2m_transform(const float* __restrict__ bx, const float* __restrict__ by,
-                                const float* __restrict__ bz, int64_t n, Aff12 T, float* __restrict__ wx,
-                                float* __restrict__ wy, float* __restrict__ wz) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float x = bx[i], y = by[i], z = bz[i];
-  wx[i] = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
-  wy[i] = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
-  wz[i] = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
-}
-
-// OpenCV's hypot (lapack.cpp): scaled, in the element type
-__device__ __forceinline__ float cv_hypot(float a, float b) {
-  a = fabsf(a);
-  b = fabsf(b);
-  if (a > b) {
-    b /= a;
-    return a * sqrtf(1 + b * b);
-  }
-  if (b > 0) {
-    a /= b;
-    return b * sqrtf(1 + a * a);
-  }
-  return 0;
-}
-
-// cv::eigen of a symmetric 3x3 float matrix: OpenCV hal::Jacobi
-// (JacobiImpl_, lapack.cpp) -- eigenvalues W descending, eigenvectors the
-// rows of V.  Fully unrolled over compile-time indices (n = 3).
-__device__ __forceinline__ void cv_jacobi3(float A[9], float W[3], float V[9]) {
-  const float eps = 1.1920928955078125e-07f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) V[k] = (k % 4 == 0) ? 1.0f : 0.0f;
-  int indR[3], indC[3];
-  W[0] = A[0];
-  W[1] = A[4];
-  W[2] = A[8];
-  // k = 0: row max over cols 1..2; k = 1: col 2 and column max over rows 0
-  indR[0] = (fabsf(A[1]) < fabsf(A[2])) ? 2 : 1;
-  indR[1] = 2;
-  indC[1] = 0;
-  indC[2] = (fabsf(A[2]) < fabsf(A[5])) ? 1 : 0;
-  for (int iters = 0; iters < 3 * 3 * 30; ++iters) {
-    int k = 0;
-    float mv = fabsf(A[indR[0]]);
-    {
-      const float val = fabsf(A[3 + indR[1]]);
-      if (mv < val) mv = val, k = 1;
-    }
-    int l = indR[k];
-    for (int i = 1; i < 3; ++i) {
-      const float val = fabsf(A[3 * indC[i] + i]);
-      if (mv < val) mv = val, k = indC[i], l = i;
-    }
-    const float p = A[3 * k + l];
-    if (fabsf(p) <= eps) break;
-    float y = (float)((W[l] - W[k]) * 0.5);
-    float t = fabsf(y) + cv_hypot(p, y);
-    float sn = cv_hypot(p, t);
-    const float c = t / sn;
-    sn = p / sn;
-    t = (p / t) * p;
-    if (y < 0) sn = -sn, t = -t;
-    A[3 * k + l] = 0;
-    W[k] -= t;
-    W[l] += t;
-    float a0, b0;
-#define SLIO_ROT(v0, v1) a0 = v0, b0 = v1, v0 = a0 * c - b0 * sn, v1 = a0 * sn + b0 * c
-    for (int i = 0; i < k; ++i) SLIO_ROT(A[3 * i + k], A[3 * i + l]);
-    for (int i = k + 1; i < l; ++i) SLIO_ROT(A[3 * k + i], A[3 * i + l]);
-    for (int i = l + 1; i < 3; ++i) SLIO_ROT(A[3 * k + i], A[3 * l + i]);
-    for (int i = 0; i < 3; ++i) SLIO_ROT(V[3 * k + i], V[3 * l + i]);
-#undef SLIO_ROT
-    for (int j = 0; j < 2; ++j) {
-      const int idx = j == 0 ? k : l;
-      if (idx < 2) {
-        int m = idx + 1;
-        float mvv = fabsf(A[3 * idx + m]);
-        for (int i = idx + 2; i < 3; ++i) {
-          const float val = fabsf(A[3 * idx + i]);
-          if (mvv < val) mvv = val, m = i;
-        }
-        indR[idx] = m;
-      }
-      if (idx > 0) {
-        int m = 0;
-        float mvv = fabsf(A[idx]);
-        for (int i = 1; i < idx; ++i) {
-          const float val = fabsf(A[3 * i + idx]);
-          if (mvv < val) mvv = val, m = i;
-        }
-        indC[idx] = m;
-      }
-    }
-  }
-  for (int k = 0; k < 2; ++k) {
-    int m = k;
-    for (int i = k + 1; i < 3; ++i)
-      if (W[m] < W[i]) m = i;
-    if (k != m) {
-      const float tw = W[m];
-      W[m] = W[k];
-      W[k] = tw;
-      for (int i = 0; i < 3; ++i) {
-        const float tv = V[3 * m + i];
-        V[3 * m + i] = V[3 * k + i];
-        V[3 * k + i] = tv;
-      }
-    }
-  }
-}
-
-// cornerOptimization's point-to-line coefficient from the five neighbours
-// (LIO-SAM :1332-1425; LeGO-LOAM's :1237-1365 is the same arithmetic)
-__device__ __forceinline__ uint8_t s2m_corner_coeff(const float (&nb)[5][3], float x0, float y0, float z0,
-                                                    float4& cf) {
-  uint8_t ok = 0;
-  float cx = 0, cy = 0, cz = 0;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    cx += nb[j][0];
-    cy += nb[j][1];
-    cz += nb[j][2];
-  }
-  cx /= 5;
-  cy /= 5;
-  cz /= 5;
-  float a11 = 0, a12 = 0, a13 = 0, a22 = 0, a23 = 0, a33 = 0;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const float ax = nb[j][0] - cx, ay = nb[j][1] - cy, az = nb[j][2] - cz;
-    a11 += ax * ax;
-    a12 += ax * ay;
-    a13 += ax * az;
-    a22 += ay * ay;
-    a23 += ay * az;
-    a33 += az * az;
-  }
-  a11 /= 5;
-  a12 /= 5;
-  a13 /= 5;
-  a22 /= 5;
-  a23 /= 5;
-  a33 /= 5;
-  float A[9] = {a11, a12, a13, a12, a22, a23, a13, a23, a33}, W[3], V[9];
-  cv_jacobi3(A, W, V);
-  if (W[0] > 3 * W[1]) {
-    const float x1 = cx + 0.1 * V[0], y1 = cy + 0.1 * V[1], z1 = cz + 0.1 * V[2];
-    const float x2 = cx - 0.1 * V[0], y2 = cy - 0.1 * V[1], z2 = cz - 0.1 * V[2];
-    const float u = (x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1);
-    const float v = (x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1);
-    const float w = (y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1);
-    const float a012 = sqrtf(u * u + v * v + w * w);
-    const float l12 = sqrtf((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2));
-    const float la = ((y1 - y2) * u + (z1 - z2) * v) / a012 / l12;
-    const float lb = -((x1 - x2) * u - (z1 - z2) * w) / a012 / l12;
-    const float lc = -((x1 - x2) * v + (y1 - y2) * w) / a012 / l12;
-    const float ld2 = a012 / l12;
-    const float s = 1 - 0.9 * fabsf(ld2);
-    cf = make_float4(s * la, s * lb, s * lc, s * ld2);
-    ok = s > 0.1;
-  }
-  return ok;
-}
-
-// surfOptimization after the plane solve (LIO-SAM :1470-1508, LeGO-LOAM
-// :1403-1447): sol = the solve's x for b = -1
-__device__ __forceinline__ uint8_t s2m_surf_coeff(const float (&sol)[3], const float (&nb)[5][3], float x0, float y0,
-                                                  float z0, float4& cf) {
-  uint8_t ok = 0;
-  float pa = sol[0], pb = sol[1], pc = sol[2], pd = 1;
-  const float ps = sqrtf(pa * pa + pb * pb + pc * pc);
-  pa /= ps;
-  pb /= ps;
-  pc /= ps;
-  pd /= ps;
-  bool valid = true;
-#pragma unroll
-  for (int j = 0; j < 5; ++j)
-    if (fabsf(pa * nb[j][0] + pb * nb[j][1] + pc * nb[j][2] + pd) > 0.2) valid = false;
-  if (valid) {
-    const float pd2 = pa * x0 + pb * y0 + pc * z0 + pd;
-    const float s = 1 - 0.9 * fabsf(pd2) / sqrtf(sqrtf(x0 * x0 + y0 * y0 + z0 * z0));
-    cf = make_float4(s * pa, s * pb, s * pc, s * pd2);
-    ok = s > 0.1;
-  }
-  return ok;
-}
-
-// coefficients (coeff.x, y, z, intensity) and selection of every scan point
-template <int KIND>  // 0: corner (point-to-line), 1: surf (point-to-plane)
-__global__ void k_s2m_coeff(const float* __restrict__ wx, const float* __restrict__ wy,
-                            const float* __restrict__ wz, int64_t n, const uint32_t* __restrict__ nbr_pos,
-                            const float* __restrict__ nbr_sqd, const float4* __restrict__ pts,
-                            float4* __restrict__ coeff, uint8_t* __restrict__ sel) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint8_t ok = 0;
-  float4 cf = make_float4(0, 0, 0, 0);
-  const float x0 = wx[i], y0 = wy[i], z0 = wz[i];
-  if (nbr_sqd[i * 5 + 4] < 1.0f) {  // (< 1.0 is false for +inf: fewer than 5 map points)
-    float nb[5][3];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const float4 p = pts[nbr_pos[i * 5 + j]];
-      nb[j][0] = p.x;
-      nb[j][1] = p.y;
-      nb[j][2] = p.z;
-    }
-    if (KIND == 0) {
-      ok = s2m_corner_coeff(nb, x0, y0, z0, cf);
-    } else {
-      float sol[3];
-      qr_solve_m1_dev(nb, sol);
-      ok = s2m_surf_coeff(sol, nb, x0, y0, z0, cf);
-    }
-  }
-  coeff[i] = cf;
-  sel[i] = ok;
-}
-
-// LMOptimization rows (:1583-1626, lidar <-> camera axis swap included) of the
-// selected points and their A^T A (21) / A^T B (6) / count, summed in double:
-// each workgroup its 256 points in a fixed tree (a butterfly over each
-// wavefront's lanes, then the four wavefronts in order), one partial per
-// workgroup.  (The 28 sequential block-wide LDS trees this replaces -- 252
-// barriers -- took 27.8 us per launch for 20k points,
-// profiles/r05_final_s2m_kernel_stats.csv.)
-struct S2mTrig {
-  float srx, crx, sry, cry, srz, crz;
-};
-constexpr int kS2mSums = 28;
-__global__ __launch_bounds__(256) void k_s2m_rows(const float* __restrict__ bx, const float* __restrict__ by,
-                                                  const float* __restrict__ bz, const float4* __restrict__ coeff,
-                                                  const uint8_t* __restrict__ sel, int64_t n, S2mTrig T,
-                                                  double* __restrict__ partial) {
-  __shared__ double red[4 * kS2mSums];
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  double v[kS2mSums];
-#pragma unroll
-  for (int k = 0; k < kS2mSums; ++k) v[k] = 0.0;
-  if (i < n && sel[i]) {
-    const float4 cs = coeff[i];
-    const float px = by[i], py = bz[i], pz = bx[i];   // lidar -> camera
-    const float cx = cs.y, cy = cs.z, cz = cs.x, ci = cs.w;
-    const float srx = T.srx, crx = T.crx, sry = T.sry, cry = T.cry, srz = T.srz, crz = T.crz;
-    const float arx = (crx * sry * srz * px + crx * crz * sry * py - srx * sry * pz) * cx +
-                      (-srx * srz * px - crz * srx * py - crx * pz) * cy +
-                      (crx * cry * srz * px + crx * cry * crz * py - cry * srx * pz) * cz;
-    const float ary = ((cry * srx * srz - crz * sry) * px + (sry * srz + cry * crz * srx) * py + crx * cry * pz) * cx +
-                      ((-cry * crz - srx * sry * srz) * px + (cry * srz - crz * srx * sry) * py - crx * sry * pz) * cz;
-    const float arz = ((crz * srx * sry - cry * srz) * px + (-cry * crz - srx * sry * srz) * py) * cx +
-                      (crx * crz * px - crx * srz * py) * cy +
-                      ((sry * srz + cry * crz * srx) * px + (crz * sry - cry * srx * srz) * py) * cz;
-    const float a[6] = {arz, arx, ary, cz, cx, cy};
-    const float b = -ci;
-    int q = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = r; c < 6; ++c) v[q++] = (double)a[r] * (double)a[c];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) v[21 + r] = (double)a[r] * (double)b;
-    v[27] = 1.0;
-  }
-  // (a + b == b + a: both lanes of a butterfly pair hold the same sum)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int k = 0; k < kS2mSums; ++k) v[k] = v[k] + __shfl_xor(v[k], off);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < kS2mSums; ++k) red[w * kS2mSums + k] = v[k];
-  __syncthreads();
-  if (threadIdx.x < kS2mSums) {
-    const int k = threadIdx.x;
-    partial[(int64_t)blockIdx.x * kS2mSums + k] =
-        ((red[k] + red[kS2mSums + k]) + red[2 * kS2mSums + k]) + red[3 * kS2mSums + k];
-  }
-}
-
-// ---- LeGO-LOAM mapping (LeGO-LOAM/src/mapOptmization.cpp) -------------------
-// pointAssociateToMap (:578-607) of the scan: see lego_to_map
-__global__ void k_lmap_transform(const float* __restrict__ bx, const float* __restrict__ by,
-                                 const float* __restrict__ bz, int64_t n, LegoRot T, float* __restrict__ wx,
-                                 float* __restrict__ wy, float* __restrict__ wz) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  lego_to_map(T, bx[i], by[i], bz[i], wx[i], wy[i], wz[i]);
-}
-
-// cornerOptimization (:1222-1370) / surfOptimization (:1372-1450) after the
-// search, and LMOptimization's rows (:1477-1537) of the same points, in ONE
-// launch: a row needs only the body point and the coefficient its thread has
-// just computed.  The corner arithmetic is LIO-SAM's (s2m_corner_coeff); the
-// plane comes from cv::solve(DECOMP_QR) on the 5 x 3 system (:1395,
-// cvs::qr_solve_mn<5, 3>), a failed solve leaving x = 0 as cv::solve does: ps
-// is then 0, everything NaN, and `s > 0.1` is false.  The rows use pointOri and
-// coeff as they are (LeGO-LOAM works in its camera-like frame throughout: no
-// axis swap) and are summed exactly as k_s2m_rows sums them.
-template <int KIND>
-__global__ __launch_bounds__(256) void k_lmap_coeff(
-    const float* __restrict__ bx, const float* __restrict__ by, const float* __restrict__ bz,
-    const float* __restrict__ wx, const float* __restrict__ wy, const float* __restrict__ wz, int64_t n,
-    const uint32_t* __restrict__ nbr_pos, const float* __restrict__ nbr_sqd, const float4* __restrict__ pts,
-    float4* __restrict__ coeff, uint8_t* __restrict__ sel, S2mTrig T, double* __restrict__ partial) {
-  __shared__ double red[4 * kS2mSums];
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  double v[kS2mSums];
-#pragma unroll
-  for (int k = 0; k < kS2mSums; ++k) v[k] = 0.0;
-  if (i < n) {
-    uint8_t ok = 0;
-    float4 cf = make_float4(0, 0, 0, 0);
-    const float x0 = wx[i], y0 = wy[i], z0 = wz[i];
-    if (nbr_sqd[i * 5 + 4] < 1.0f) {  // (false for +inf: fewer than 5 map points)
-      float nb[5][3];
-#pragma unroll
-      for (int j = 0; j < 5; ++j) {
-        const float4 p = pts[nbr_pos[i * 5 + j]];
-        nb[j][0] = p.x;
-        nb[j][1] = p.y;
-        nb[j][2] = p.z;
-      }
-      if (KIND == 0) {
-        ok = s2m_corner_coeff(nb, x0, y0, z0, cf);
-      } else {
-        const float m1[5] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f};
-        float sol[3];
-        if (!slio::cvs::qr_solve_mn<5, 3>(&nb[0][0], m1, sol)) sol[0] = sol[1] = sol[2] = 0.0f;
-        ok = s2m_surf_coeff(sol, nb, x0, y0, z0, cf);
-      }
-    }
-    coeff[i] = cf;
-    sel[i] = ok;
-    if (ok) {
-      const float px = bx[i], py = by[i], pz = bz[i];
-      const float cx = cf.x, cy = cf.y, cz = cf.z;
-      const float srx = T.srx, crx = T.crx, sry = T.sry, cry = T.cry, srz = T.srz, crz = T.crz;
-      const float arx = (crx * sry * srz * px + crx * crz * sry * py - srx * sry * pz) * cx +
-                        (-srx * srz * px - crz * srx * py - crx * pz) * cy +
-                        (crx * cry * srz * px + crx * cry * crz * py - cry * srx * pz) * cz;
-      const float ary = ((cry * srx * srz - crz * sry) * px + (sry * srz + cry * crz * srx) * py + crx * cry * pz) * cx +
-                        ((-cry * crz - srx * sry * srz) * px + (cry * srz - crz * srx * sry) * py - crx * sry * pz) * cz;
-      const float arz = ((crz * srx * sry - cry * srz) * px + (-cry * crz - srx * sry * srz) * py) * cx +
-                        (crx * crz * px - crx * srz * py) * cy +
-                        ((sry * srz + cry * crz * srx) * px + (crz * sry - cry * srx * srz) * py) * cz;
-      const float a[6] = {arx, ary, arz, cx, cy, cz};
-      const float b = -cf.w;
-      int q = 0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = r; c < 6; ++c) v[q++] = (double)a[r] * (double)a[c];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) v[21 + r] = (double)a[r] * (double)b;
-      v[27] = 1.0;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int k = 0; k < kS2mSums; ++k) v[k] = v[k] + __shfl_xor(v[k], off);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < kS2mSums; ++k) red[w * kS2mSums + k] = v[k];
-  __syncthreads();
-  if (threadIdx.x < kS2mSums) {
-    const int k = threadIdx.x;
-    partial[(int64_t)blockIdx.x * kS2mSums + k] =
-        ((red[k] + red[kS2mSums + k]) + red[2 * kS2mSums + k]) + red[3 * kS2mSums + k];
-  }
-}
-
-// float4 xyzi (the front-end's clouds) -> SoA, for the VoxelGrid
-__global__ void k_lmap_split4(const float4* __restrict__ in, int64_t n, float* __restrict__ x,
-                              float* __restrict__ y, float* __restrict__ z) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = in[i];
-  x[i] = p.x;
-  y[i] = p.y;
-  z[i] = p.z;
-}
-
-// the six cached float sines and cosines (:562-576 / :609-622) of
-// {rx, ry, rz, tx, ty, tz}: roll = rx, pitch = ry, yaw = rz
-static LegoRot lmap_rot(const float tf[6]) {
-  auto fc = [](float a) { return (float)std::cos((double)a); };
-  auto fs = [](float a) { return (float)std::sin((double)a); };
-  return LegoRot{fc(tf[0]), fs(tf[0]), fc(tf[1]), fs(tf[1]), fc(tf[2]), fs(tf[2]), tf[3], tf[4], tf[5]};
-}
-
-// pcl::getTransformation (pcl/common/impl/eigen.hpp) in float, the trig
-// correctly rounded (evaluated in double)
-static Aff12 s2m_affine(const float tf[6]) {
-  const float x = tf[3], y = tf[4], z = tf[5], roll = tf[0], pitch = tf[1], yaw = tf[2];
-  auto fc = [](float a) { return (float)std::cos((double)a); };
-  auto fs = [](float a) { return (float)std::sin((double)a); };
-  const float A = fc(yaw), B = fs(yaw), C = fc(pitch), D = fs(pitch), E = fc(roll), F = fs(roll), DE = D * E,
-              DF = D * F;
-  Aff12 t;
-  t.m[0] = A * C, t.m[1] = A * DF - B * E, t.m[2] = B * F + A * DE, t.m[3] = x;
-  t.m[4] = B * C, t.m[5] = A * E + B * DF, t.m[6] = B * DE - A * F, t.m[7] = y;
-  t.m[8] = -D, t.m[9] = C * F, t.m[10] = C * E, t.m[11] = z;
-  return t;
-}
-
-extern "C" {
-
-int slio_s2m_coeffs(slio_handle h, int kind, const float transform[6], int64_t* nsel) {
-  SLIO_CHECK_H(h);
-  Ctx& c = h->c;
-  if ((kind != 0 && kind != 1) || !transform) {
-    set_error("slio_s2m_coeffs: bad arguments");
-    return SLIO_EINVAL;
-  }
-  if (!c.map || !c.bx) {
-    set_error("slio_s2m_coeffs: map and scan needed");
-    return SLIO_ESTATE;
-  }
-  if (c.prm.nranks != 1) {
-    set_error("slio_s2m_coeffs: single-rank handles only");
-    return SLIO_EINVAL;
-  }
-  const int64_t n = c.n;
-  if (!c.wbx) {
-    const int64_t cap = c.prm.max_points;
-    hipError_t e;
-    if ((e = hipMalloc(&c.wbx, 4 * cap)) || (e = hipMalloc(&c.wby, 4 * cap)) || (e = hipMalloc(&c.wbz, 4 * cap))) {
-      set_error(std::string("slio_s2m_coeffs: hipMalloc: ") + hipGetErrorString(e));
-      return SLIO_ENOMEM;
-    }
-  }
-  if (n > 0) {
-    k_s2m_transform<<<grid_blocks(n), 256, 0, c.stream>>>(c.bx, c.by, c.bz, n, s2m_affine(transform), c.wbx,
-                                                           c.wby, c.wbz);
-    // the 5-NN of the world points: the search pass in kNN-only mode with the
-    // identity pose (body -> world of an identity pose is exact in float)
-    slio_pose idp{};
-    idp.rot[0] = 1.0;
-    idp.rli[0] = 1.0;
-    const PoseDev P = make_pose(&idp);
-    const ScanDev sd{c.wbx, c.wby, c.wbz, n};
-    if (int rc = enqueue_pass(c, &P, nullptr, 1, 0, nullptr, false, true, &sd)) return rc;
-    std::shared_lock<std::shared_mutex> lk(c.map->mu);
-    if (int rc = map_read_sync(c)) return rc;
-    if (kind == 0)
-      k_s2m_coeff<0><<<grid_blocks(n), 256, 0, c.stream>>>(c.wbx, c.wby, c.wbz, n, c.nbr_pos, c.nbr_sqd,
-                                                            c.map->pts, c.plane, c.sel);
-    else
-      k_s2m_coeff<1><<<grid_blocks(n), 256, 0, c.stream>>>(c.wbx, c.wby, c.wbz, n, c.nbr_pos, c.nbr_sqd,
-                                                            c.map->pts, c.plane, c.sel);
-    SLIO_HIP(hipGetLastError());
-  }
-  c.s2m_kind = kind;
-  if (nsel) {
-    std::vector<uint8_t> sl((size_t)n);
-    if (n) {
-      SLIO_HIP(hipStreamSynchronize(c.stream));
-      SLIO_HIP(hipMemcpy(sl.data(), c.sel, n, hipMemcpyDeviceToHost));
-    }
-    int64_t k = 0;
-    for (uint8_t v : sl) k += v;
-    *nsel = k;
-  }
-  return SLIO_OK;
-}
-
-int slio_s2m_get_coeffs(slio_handle h, float* coeff, uint8_t* sel) {
-  SLIO_CHECK_H(h);
-  Ctx& c = h->c;
-  if (c.n > 0) {
-    SLIO_HIP(hipStreamSynchronize(c.stream));
-    if (coeff) SLIO_HIP(hipMemcpy(coeff, c.plane, 16 * c.n, hipMemcpyDeviceToHost));
-    if (sel) SLIO_HIP(hipMemcpy(sel, c.sel, c.n, hipMemcpyDeviceToHost));
-  }
-  return SLIO_OK;
-}
-
-int slio_s2m_normal_equations(slio_handle h_corner, slio_handle h_surf, const float transform[6], float AtA[36],
-                              float AtB[6], int64_t* nsel) {
-  if (!transform || !AtA || !AtB) {
-    set_error("slio_s2m_normal_equations: bad arguments");
-    return SLIO_EINVAL;
-  }
-  // the camera-frame trig of LMOptimization (:1564-1569), float sin / cos
-  S2mTrig T;
-  auto fc = [](float a) { return (float)std::cos((double)a); };
-  auto fs = [](float a) { return (float)std::sin((double)a); };
-  T.srx = fs(transform[1]), T.crx = fc(transform[1]);
-  T.sry = fs(transform[2]), T.cry = fc(transform[2]);
-  T.srz = fs(transform[0]), T.crz = fc(transform[0]);
-  double acc[kS2mSums] = {0};
-  // corners first, then surfs (combineOptimizationCoeffs :1517-1543); both
-  // clouds' rows launched before either is read back (their own streams)
-  slio_handle hs2[2] = {h_corner, h_surf};
-  for (slio_handle h : hs2) {
-    if (!h || h->c.n == 0) continue;
-    Ctx& c = h->c;
-    const int nb = (int)((c.n + 255) / 256);
-    k_s2m_rows<<<nb, 256, 0, c.stream>>>(c.bx, c.by, c.bz, c.plane, c.sel, c.n, T, c.chunk_part);
-    SLIO_HIP(hipGetLastError());
-  }
-  for (slio_handle h : hs2) {
-    if (!h || h->c.n == 0) continue;
-    Ctx& c = h->c;
-    const int nb = (int)((c.n + 255) / 256);
-    std::vector<double> part((size_t)nb * kS2mSums);
-    const Rb rb{part.data(), c.chunk_part, 8 * part.size()};
-    SLIO_HIP(readback(c.stream, &rb, 1));
-    for (int b = 0; b < nb; ++b)
-      for (int k = 0; k < kS2mSums; ++k) acc[k] = acc[k] + part[(size_t)b * kS2mSums + k];
-  }
-  int q = 0;
-  for (int r = 0; r < 6; ++r)
-    for (int cc = r; cc < 6; ++cc, ++q) AtA[6 * r + cc] = AtA[6 * cc + r] = (float)acc[q];
-  for (int r = 0; r < 6; ++r) AtB[r] = (float)acc[21 + r];
-  if (nsel) *nsel = (int64_t)llround(acc[27]);
-  return SLIO_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- LIO-SAM loop closure: one ICP pass
-// performLoopClosure's pcl::IterativeClosestPoint (mapOptmization.cpp:766-780)
-// as PCL 1.10 runs it (the reference tree carries no PCL source; slio.h
-// restates the rules): per iteration transformCloud of the working cloud,
-// CorrespondenceEstimation::determineCorrespondences (1-NN, distance gate)
-// and the sums TransformationEstimationSVD needs -- ONE launch.  The handle's
-// map is the target, its scan the source.  One query per lane on the 3x3x3
-// fine cells around it; a query whose nearest is not certified there
-// (outside_bound, as the search pass's block step) is deferred to the
-// workgroup's far queue and answered by a whole wavefront on the coarse level
-// (far_search<U, 1>).  A loop candidate starts metres from where it belongs:
-// in the first passes most queries take the far path.  Keys are those of the
-// search pass (float squared distance, then position in the cell-sorted
-// points), so the nearest point equals entry 0 of slio_get_neighbors for the
-// same world point, ties included.
-// The 16 sums (+ the count, + the far queries) are reduced as k_s2m_rows
-// reduces its rows: a butterfly over each wavefront, the four wavefronts in
-// order, one partial per workgroup.
-constexpr int kIcpSums = 18;  // p (3), q (3), q p^T (9), sqd, correspondences, far queries
-// (sx / sy / sz may be wx / wy / wz: no __restrict__ on the six)
-__global__ __launch_bounds__(256) void k_icp_pass(const MapView map, const float* sx, const float* sy,
-                                                  const float* sz, int64_t n, Aff12 T, double max_sq, float* wx,
-                                                  float* wy, float* wz, int32_t* __restrict__ idx,
-                                                  float* __restrict__ sqd, double* __restrict__ partial) {
-  __shared__ double red[4 * kIcpSums];
-  __shared__ int far_cnt;
-  __shared__ float4 far_q[256];
-  __shared__ uint8_t far_slot[256];
-  __shared__ uint64_t far_key[256];
-  __shared__ uint32_t far_pre[4][64], far_beg[4][64];
-  const int tid = threadIdx.x;
-  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-  const GridGeom g = map.g;
-  const float INF = __int_as_float(0x7f800000);
-  if (tid == 0) far_cnt = 0;
-  __syncthreads();
-  const bool live = i < n;
-  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  if (live) {
-    // (in place when sx is wx: each lane reads its own point before it writes it)
-    const float x = sx[i], y = sy[i], z = sz[i];
-    qx = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
-    qy = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
-    qz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
-    wx[i] = qx;
-    wy[i] = qy;
-    wz[i] = qz;
-  }
-  const bool finite = live && isfinite(qx) && isfinite(qy) && isfinite(qz) && map.n > 0;
-  uint64_t best = kInfKey;
-  bool done = !finite;
-  if (finite) {
-    const int cx = cell_coord(qx, g.ox, g.inv_h), cy = cell_coord(qy, g.oy, g.inv_h),
-              cz = cell_coord(qz, g.oz, g.inv_h);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dx - 1);
-    if (x0 <= x1)
-      for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy) {
-          const int y = cy + dy, z = cz + dz;
-          if (y < 0 || y >= g.dy || z < 0 || z >= g.dz) continue;
-          const int64_t rb = ((int64_t)z * g.dy + y) * g.dx;
-          const uint32_t s = map.start[rb + x0], e = map.start[rb + x1 + 1];
-          for (uint32_t a = s; a < e; ++a) {
-            const float4 c = map.pts[a];
-            const float ddx = qx - c.x, ddy = qy - c.y, ddz = qz - c.z;
-            const float d = (ddx * ddx + ddy * ddy) + ddz * ddz;  // as consider()
-            const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint64_t)a;
-            best = key < best ? key : best;
-          }
-        }
-    bool covers;
-    const float b1 = outside_bound(g, cx, cy, cz, 1, qx, qy, qz, covers);
-    const float d1 = __uint_as_float((uint32_t)(best >> 32));
-    done = covers || (best != kInfKey && b1 > 0.0f && d1 < (b1 * b1) * 0.99999f);
-    if (!done) {
-      const int k = atomicAdd(&far_cnt, 1);
-      far_slot[k] = (uint8_t)tid;
-      far_q[k] = make_float4(qx, qy, qz, best != kInfKey ? d1 : INF);  // a real point's distance bounds the search
-    }
-  }
-  __syncthreads();
-  const int nfar = far_cnt;
-  for (int k = tid >> 6; k < nfar; k += 4) {  // (uniform per wavefront)
-    const float4 q = far_q[k];
-    Top5 tf;
-    far_search<4, 1>(map, q.x, q.y, q.z, q.w, far_pre[tid >> 6], far_beg[tid >> 6], tf);
-    if ((tid & 63) == 0) far_key[far_slot[k]] = tf.k[0];
-  }
-  __syncthreads();
-  const bool was_far = finite && !done;
-  if (was_far) best = far_key[tid];
-  double v[kIcpSums];
-#pragma unroll
-  for (int k = 0; k < kIcpSums; ++k) v[k] = 0.0;
-  if (live) {
-    int32_t id = -1;
-    float d = INF;
-    if (best != kInfKey) {
-      const float4 c = map.pts[(uint32_t)best];
-      d = __uint_as_float((uint32_t)(best >> 32));
-      // CorrespondenceEstimation: `if (distance > max_dist_sqr) continue;`
-      if ((double)d <= max_sq) {
-        id = (int32_t)__float_as_uint(c.w);
-        const float p[3] = {qx, qy, qz}, m[3] = {c.x, c.y, c.z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          v[a] = (double)p[a];
-          v[3 + a] = (double)m[a];
-#pragma unroll
-          for (int b = 0; b < 3; ++b) v[6 + 3 * a + b] = (double)m[a] * (double)p[b];
-        }
-        v[15] = (double)d;
-        v[16] = 1.0;
-      }
-    }
-    idx[i] = id;
-    sqd[i] = d;
-  }
-  v[17] = was_far ? 1.0 : 0.0;
-  // (a + b == b + a: both lanes of a butterfly pair hold the same sum)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int k = 0; k < kIcpSums; ++k) v[k] = v[k] + __shfl_xor(v[k], off);
-  const int w = tid >> 6;
-  if ((tid & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < kIcpSums; ++k) red[w * kIcpSums + k] = v[k];
-  __syncthreads();
-  if (tid < kIcpSums)
-    partial[(int64_t)blockIdx.x * kIcpSums + tid] =
-        ((red[tid] + red[kIcpSums + tid]) + red[2 * kIcpSums + tid]) + red[3 * kIcpSums + tid];
-}
-
-extern "C" {
-
-int slio_icp_correspond(slio_handle h, const float T[16], int from_scan, double max_dist, double sums[16],
-                        int64_t* ncorr) {
-  if (!h) {
-    set_error("null handle");
-    return SLIO_EINVAL;
-  }
-  if (!T || !sums || !ncorr || (from_scan != 0 && from_scan != 1) || !(max_dist >= 0.0) ||
-      h->c.prm.nranks != 1) {
-    set_error("slio_icp_correspond: bad arguments");
-    return SLIO_EINVAL;
-  }
-  Ctx& c = h->c;
-  if (!c.map || (from_scan && !c.bx && c.n > 0) || (!from_scan && c.icp_n < 0)) {
-    set_error(from_scan || !c.map ? "slio_icp_correspond: map and scan needed"
-                                  : "slio_icp_correspond: no working cloud (from_scan = 1 first)");
-    return SLIO_ESTATE;
-  }
-  SLIO_HIP(hipSetDevice(c.prm.device));
-  const int64_t n = from_scan ? c.n : c.icp_n;
-  for (int k = 0; k < 16; ++k) sums[k] = 0.0;
-  *ncorr = 0;
-  c.icp_far = 0;
-  c.icp_n = n;
-  if (n == 0) return SLIO_OK;
-  const int nb = (int)((n + 255) / 256);
-  hipError_t e;
-  if ((e = MapDev::take(c.icp[0], 12 * n)) || (e = MapDev::take(c.icp[1], 4 * n)) ||
-      (e = MapDev::take(c.icp[2], 4 * n)) || (e = MapDev::take(c.icp[3], 8 * (size_t)kIcpSums * nb))) {
-    c.icp_n = -1;
-    set_error(std::string("slio_icp_correspond: hipMalloc: ") + hipGetErrorString(e));
-    return SLIO_ENOMEM;
-  }
-  float* wx = (float*)c.icp[0].p;
-  float* wy = wx + n;
-  float* wz = wx + 2 * n;
-  double* part = (double*)c.icp[3].p;
-  Aff12 A;
-  std::memcpy(A.m, T, sizeof(A.m));
-  if (int rc = map_refresh(c); rc) return rc;
-  {
-    std::shared_lock<std::shared_mutex> lk(c.map->mu);
-    if (int rc = map_read_sync(c)) return rc;
-    const CoarseView cv{c.map->cg, c.map->clo, c.map->chi};
-    const MapView mv{c.map->g,      c.map->n,    c.map->pts,    c.map->start, c.map->blk,
-                     c.map->bstart, c.map->nblk, c.map->ncells, cv};
-    k_icp_pass<<<nb, 256, 0, c.stream>>>(mv, from_scan ? c.bx : wx, from_scan ? c.by : wy, from_scan ? c.bz : wz, n,
-                                         A, max_dist * max_dist, wx, wy, wz, (int32_t*)c.icp[1].p,
-                                         (float*)c.icp[2].p, part);
-    SLIO_HIP(hipGetLastError());
-  }
-  std::vector<double> hp((size_t)nb * kIcpSums);
-  const Rb rb{hp.data(), part, 8 * hp.size()};
-  SLIO_HIP(readback(c.stream, &rb, 1));
-  double acc[kIcpSums] = {0};
-  for (int b = 0; b < nb; ++b)
-    for (int k = 0; k < kIcpSums; ++k) acc[k] = acc[k] + hp[(size_t)b * kIcpSums + k];
-  for (int k = 0; k < 16; ++k) sums[k] = acc[k];
-  *ncorr = (int64_t)llround(acc[16]);
-  c.icp_far = (int64_t)llround(acc[17]);
-  return SLIO_OK;
-}
-
-int slio_icp_get_correspondences(slio_handle h, int32_t* idx, float* sqd) {
-  SLIO_CHECK_H(h);
-  Ctx& c = h->c;
-  if (c.icp_n < 0) {
-    set_error("slio_icp_get_correspondences: no pass yet");
-    return SLIO_ESTATE;
-  }
-  if (c.icp_n > 0) {
-    SLIO_HIP(hipStreamSynchronize(c.stream));
-    if (idx) SLIO_HIP(hipMemcpy(idx, c.icp[1].p, 4 * c.icp_n, hipMemcpyDeviceToHost));
-    if (sqd) SLIO_HIP(hipMemcpy(sqd, c.icp[2].p, 4 * c.icp_n, hipMemcpyDeviceToHost));
-  }
-  return SLIO_OK;
-}
-
-int slio_icp_get_working(slio_handle h, float* x, float* y, float* z, int64_t cap, int64_t* n) {
-  SLIO_CHECK_H(h);
-  Ctx& c = h->c;
-  if (c.icp_n < 0) {
-    set_error("slio_icp_get_working: no pass yet");
-    return SLIO_ESTATE;
-  }
-  if (n) *n = c.icp_n;
-  if (cap < c.icp_n || (c.icp_n > 0 && (!x || !y || !z))) {
-    set_error("slio_icp_get_working: buffer too small");
-    return SLIO_ECAPACITY;
-  }
-  if (c.icp_n > 0) {
-    const float* w = (const float*)c.icp[0].p;
-    SLIO_HIP(hipStreamSynchronize(c.stream));
-    SLIO_HIP(hipMemcpy(x, w, 4 * c.icp_n, hipMemcpyDeviceToHost));
-    SLIO_HIP(hipMemcpy(y, w + c.icp_n, 4 * c.icp_n, hipMemcpyDeviceToHost));
-    SLIO_HIP(hipMemcpy(z, w + 2 * c.icp_n, 4 * c.icp_n, hipMemcpyDeviceToHost));
-  }
-  return SLIO_OK;
-}
-
-int slio_icp_far_queries(slio_handle h, int64_t* n) {
-  if (!h || !n) {
-    set_error(h ? "slio_icp_far_queries: bad arguments" : "null handle");
-    return SLIO_EINVAL;
-  }
-  *n = h->c.icp_far;
-  return SLIO_OK;
-}
-
-}  // extern "C"
 
 // ---------------------------------------------------------------- scan undistortion
 struct UndistEnd {
@@ -8525,203 +7108,13 @@ int slio_iterate_async(slio_handle h, const slio_pose* x, int do_search, int ext
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- LIO-SAM keyframe store and local map
-// saveKeyFramesAndFactor's cornerCloudKeyFrames / surfCloudKeyFrames
-// (mapOptmization.cpp:2069-2077) and extractCloud (:1204-1251) on the device.
-
-// room for n more points in the arena (grown by half, the stored keyframes
-// copied on the stream; hipFree waits for the copy)
-static int kf_reserve(Ctx& c, int64_t n, const char* who) {
-  if (c.kf_used + n <= c.kf_cap) return SLIO_OK;
-  const int64_t cap = std::max<int64_t>(c.kf_used + n + (c.kf_used + n) / 2, 1 << 16);
-  float* q[3] = {nullptr, nullptr, nullptr};
-  float* const old[3] = {c.kfx, c.kfy, c.kfz};
-  hipError_t e = hipSuccess;
-  for (int a = 0; a < 3 && !e; ++a) {
-    e = hipMalloc(&q[a], 4 * cap);
-    if (!e && c.kf_used > 0) e = hipMemcpyAsync(q[a], old[a], 4 * c.kf_used, hipMemcpyDeviceToDevice, c.stream);
-  }
-  if (!e) e = hipStreamSynchronize(c.stream);
-  if (e) {
-    (void)hipGetLastError();
-    for (float* p : q)
-      if (p) (void)hipFree(p);
-    set_error(std::string(who) + ": keyframe arena: " + hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? SLIO_ENOMEM : SLIO_EDEVICE;
-  }
-  for (float* p : old)
-    if (p) (void)hipFree(p);
-  c.kfx = q[0];
-  c.kfy = q[1];
-  c.kfz = q[2];
-  c.kf_cap = cap;
-  return SLIO_OK;
-}
-
-static void kf_append(Ctx& c, int64_t n, int32_t* key_index) {
-  if (key_index) *key_index = (int32_t)c.kf_off.size();
-  c.kf_off.push_back(c.kf_used);
-  c.kf_len.push_back(n);
-  c.kf_used += n;
-}
-
-#define SLIO_KF_ARGS(cond, who)                  \
-  do {                                           \
-    if (!h) {                                    \
-      set_error("null handle");                  \
-      return SLIO_EINVAL;                        \
-    }                                            \
-    if (cond) {                                  \
-      set_error(who ": bad arguments");          \
-      return SLIO_EINVAL;                        \
-    }                                            \
-  } while (0)
-
-extern "C" {
-
-int slio_s2m_kf_push(slio_handle h, const float* x, const float* y, const float* z, int64_t n,
-                     int32_t* key_index) {
-  SLIO_KF_ARGS(n < 0 || (n > 0 && (!x || !y || !z)) || n > INT32_MAX, "slio_s2m_kf_push");
-  Ctx& c = h->c;
-  if (c.kf_off.size() >= (size_t)INT32_MAX) {
-    set_error("slio_s2m_kf_push: too many keyframes");
-    return SLIO_ECAPACITY;
-  }
-  SLIO_HIP(hipSetDevice(c.prm.device));
-  if (n > 0) {
-    if (int rc = kf_reserve(c, n, "slio_s2m_kf_push")) return rc;
-    const int64_t o = c.kf_used;
-    SLIO_HIP(hipMemcpyAsync(c.kfx + o, x, 4 * n, hipMemcpyHostToDevice, c.stream));
-    SLIO_HIP(hipMemcpyAsync(c.kfy + o, y, 4 * n, hipMemcpyHostToDevice, c.stream));
-    SLIO_HIP(hipMemcpyAsync(c.kfz + o, z, 4 * n, hipMemcpyHostToDevice, c.stream));
-  }
-  kf_append(c, n, key_index);
-  return SLIO_OK;
-}
-
-int slio_s2m_kf_push_scan(slio_handle h, int32_t* key_index) {
-  SLIO_KF_ARGS(false, "slio_s2m_kf_push_scan");
-  Ctx& c = h->c;
-  if (!c.bx) {
-    set_error("slio_s2m_kf_push_scan: no scan uploaded");
-    return SLIO_ESTATE;
-  }
-  if (c.kf_off.size() >= (size_t)INT32_MAX) {
-    set_error("slio_s2m_kf_push_scan: too many keyframes");
-    return SLIO_ECAPACITY;
-  }
-  SLIO_HIP(hipSetDevice(c.prm.device));
-  const int64_t n = c.n;
-  if (n > 0) {
-    if (int rc = kf_reserve(c, n, "slio_s2m_kf_push_scan")) return rc;
-    const int64_t o = c.kf_used;
-    SLIO_HIP(hipMemcpyAsync(c.kfx + o, c.bx, 4 * n, hipMemcpyDeviceToDevice, c.stream));
-    SLIO_HIP(hipMemcpyAsync(c.kfy + o, c.by, 4 * n, hipMemcpyDeviceToDevice, c.stream));
-    SLIO_HIP(hipMemcpyAsync(c.kfz + o, c.bz, 4 * n, hipMemcpyDeviceToDevice, c.stream));
-  }
-  kf_append(c, n, key_index);
-  return SLIO_OK;
-}
-
-int slio_s2m_kf_info(slio_handle h, int32_t* nkeys, int64_t* npoints) {
-  SLIO_KF_ARGS(false, "slio_s2m_kf_info");
-  if (nkeys) *nkeys = (int32_t)h->c.kf_off.size();
-  if (npoints) *npoints = h->c.kf_used;
-  return SLIO_OK;
-}
-
-int slio_s2m_kf_sizes(slio_handle h, int64_t* sizes, int64_t cap) {
-  SLIO_KF_ARGS(cap < 0 || (cap > 0 && !sizes), "slio_s2m_kf_sizes");
-  const auto& len = h->c.kf_len;
-  if (cap < (int64_t)len.size()) {
-    set_error("slio_s2m_kf_sizes: buffer too small");
-    return SLIO_ECAPACITY;
-  }
-  for (size_t k = 0; k < len.size(); ++k) sizes[k] = len[k];
-  return SLIO_OK;
-}
-
-int slio_s2m_kf_clear(slio_handle h) {
-  SLIO_KF_ARGS(false, "slio_s2m_kf_clear");
-  // (the arena stays allocated; an assembly still in flight on the stream
-  // reads it before any later push writes it: one stream)
-  h->c.kf_off.clear();
-  h->c.kf_len.clear();
-  h->c.kf_used = 0;
-  return SLIO_OK;
-}
-
-int slio_s2m_kf_get(slio_handle h, int32_t key, float* x, float* y, float* z, int64_t cap, int64_t* n) {
-  SLIO_KF_ARGS(key < 0 || (size_t)key >= h->c.kf_off.size() || cap < 0, "slio_s2m_kf_get");
-  Ctx& c = h->c;
-  const int64_t len = c.kf_len[key], o = c.kf_off[key];
-  if (n) *n = len;
-  if (cap < len || (len > 0 && (!x || !y || !z))) {
-    set_error("slio_s2m_kf_get: buffer too small");
-    return SLIO_ECAPACITY;
-  }
-  if (len > 0) {
-    SLIO_HIP(hipSetDevice(c.prm.device));
-    SLIO_HIP(hipStreamSynchronize(c.stream));
-    SLIO_HIP(hipMemcpy(x, c.kfx + o, 4 * len, hipMemcpyDeviceToHost));
-    SLIO_HIP(hipMemcpy(y, c.kfy + o, 4 * len, hipMemcpyDeviceToHost));
-    SLIO_HIP(hipMemcpy(z, c.kfz + o, 4 * len, hipMemcpyDeviceToHost));
-  }
-  return SLIO_OK;
-}
-
-}  // extern "C"
-
-// The segment table of an assembly: for i in list order keyframe key_ind[i]
-// of every store in src[0..nsrc), at pose poses6[6 i ..]; non-empty entries
-// only, so a tile of the gather touches at most one segment per point.  No
-// device call.
-// form 0: poses6 = {roll, pitch, yaw, x, y, z} as a float affine (LIO-SAM);
-// form 1: poses6 = LeGO-LOAM's {rx, ry, rz, tx, ty, tz} as a LegoRot
-static int kf_segments(const Ctx* const* src, int nsrc, const int32_t* key_ind, const float* poses6, int32_t nsel,
-                       std::vector<KfSeg>& seg, int64_t& n, const char* who, int form = 0) {
-  n = 0;
-  for (int32_t i = 0; i < nsel; ++i) {
-    const int32_t k = key_ind[i];
-    if (k < 0 || (size_t)k >= src[0]->kf_off.size()) {
-      set_error(std::string(who) + ": key index " + std::to_string(k) + " out of range");
-      return SLIO_EINVAL;
-    }
-    Aff12 T{};
-    if (form == 0) {
-      T = s2m_affine(poses6 + 6 * (int64_t)i);
-    } else {
-      const LegoRot R = lmap_rot(poses6 + 6 * (int64_t)i);
-      std::memcpy(T.m, &R, sizeof(R));
-    }
-    for (int a = 0; a < nsrc; ++a) {
-      const Ctx& sc = *src[a];
-      if (sc.kf_len[k] == 0) continue;
-      // the (int)n radix sorts of the VoxelGrid and of build_index
-      if (n + sc.kf_len[k] > (int64_t)INT32_MAX) {
-        set_error(std::string(who) + ": more than 2^31 - 1 points selected");
-        return SLIO_ECAPACITY;
-      }
-      KfSeg s;
-      s.x = sc.kfx + sc.kf_off[k];
-      s.y = sc.kfy + sc.kf_off[k];
-      s.z = sc.kfz + sc.kf_off[k];
-      s.off = (uint32_t)n;
-      s.pad = 0;
-      std::memcpy(s.m, T.m, sizeof(s.m));
-      seg.push_back(s);
-      n += sc.kf_len[k];
-    }
-  }
-  return SLIO_OK;
-}
-
 // Gather-transform the n points of `seg` into one concatenation on c's
 // stream, VoxelGrid it with edge `leaf`, and make the result c's map
-// (slio_s2m_map_from_keyframes, slio_s2m_loop_cloud) or c's scan
-// (slio_s2m_loop_cloud, as_scan).
-static int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float leaf, bool as_scan,
-                       int64_t counts[2], const char* who, int form = 0) {
+// (slio_s2m_map_from_keyframes, slio_s2m_loop_cloud, slio_lmap_extract) or
+// c's scan (slio_s2m_loop_cloud, as_scan).  The callers are in
+// slio_mapopt.hip; the VoxelGrid and the index build it drives stay here.
+int slio::kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float leaf, bool as_scan,
+                      int64_t counts[2], const char* who, int form) {
   hipStream_t st = c.stream;
   int rc = nbr_settle_shared(c);  // the map (scan) it was searched on (with) is replaced
   if (rc) return rc;
@@ -8858,508 +7251,6 @@ static int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float l
   }
   return SLIO_OK;
 }
-
-extern "C" {
-
-int slio_s2m_map_from_keyframes(slio_handle h, const int32_t* key_ind, const float* poses6, int32_t nsel,
-                                float leaf, int64_t counts[2]) {
-  static const char* who = "slio_s2m_map_from_keyframes";
-  SLIO_KF_ARGS(nsel < 0 || (nsel > 0 && (!key_ind || !poses6)) || !(leaf > 0.0f), "slio_s2m_map_from_keyframes");
-  Ctx& c = h->c;
-  std::vector<KfSeg> seg;
-  int64_t n = 0;
-  const Ctx* src[1] = {&c};
-  if (int rc = kf_segments(src, 1, key_ind, poses6, nsel, seg, n, who)) return rc;
-  SLIO_HIP(hipSetDevice(c.prm.device));
-  return kf_assemble(c, seg, n, leaf, false, counts, who);
-}
-
-int slio_s2m_loop_cloud(slio_handle h_dst, slio_handle h_corner, slio_handle h_surf, const int32_t* key_ind,
-                        const float* poses6, int32_t nsel, float leaf, int as_scan, int64_t counts[2]) {
-  static const char* who = "slio_s2m_loop_cloud";
-  if (!h_dst || !h_corner || !h_surf) {
-    set_error("null handle");
-    return SLIO_EINVAL;
-  }
-  if (nsel < 0 || (nsel > 0 && (!key_ind || !poses6)) || !(leaf > 0.0f) || (as_scan != 0 && as_scan != 1)) {
-    set_error("slio_s2m_loop_cloud: bad arguments");
-    return SLIO_EINVAL;
-  }
-  Ctx& c = h_dst->c;
-  Ctx* const srcs[2] = {&h_corner->c, &h_surf->c};
-  for (const Ctx* s : {(const Ctx*)&c, (const Ctx*)srcs[0], (const Ctx*)srcs[1]})
-    if (s->prm.nranks != 1 || s->prm.device != c.prm.device) {
-      set_error("slio_s2m_loop_cloud: single-rank handles on one device only");
-      return SLIO_EINVAL;
-    }
-  if (srcs[0]->kf_off.size() != srcs[1]->kf_off.size()) {
-    set_error("slio_s2m_loop_cloud: the corner and surf stores hold different numbers of keyframes");
-    return SLIO_EINVAL;
-  }
-  std::vector<KfSeg> seg;
-  int64_t n = 0;
-  const Ctx* src[2] = {srcs[0], srcs[1]};
-  if (int rc = kf_segments(src, 2, key_ind, poses6, nsel, seg, n, who)) return rc;
-  SLIO_HIP(hipSetDevice(c.prm.device));
-  // the stores' pushes (copies on their own streams) come before the gather
-  if (n > 0)
-    for (Ctx* s : srcs) {
-      if (s == &c || s->stream == c.stream || (s == srcs[1] && srcs[1] == srcs[0])) continue;
-      if (!s->kf_ev) SLIO_HIP(hipEventCreateWithFlags(&s->kf_ev, hipEventDisableTiming));
-      SLIO_HIP(hipEventRecord(s->kf_ev, s->stream));
-      SLIO_HIP(hipStreamWaitEvent(c.stream, s->kf_ev, 0));
-    }
-  return kf_assemble(c, seg, n, leaf, as_scan != 0, counts, who);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- LeGO-LOAM mapping
-// mapOptmization.cpp of LeGO-LOAM with loopClosureEnableFlag = false
-// (slio_lmap_*, slio.h): downsampleCurrentScan from the front-end's device
-// clouds, extractSurroundingKeyFrames' map assembly from three keyframe
-// stores, cornerOptimization / surfOptimization / LMOptimization's rows
-// (k_lmap_coeff) and scan2MapOptimization's loop.  The mapper owns four
-// handles that share one stream, so every stage is ordered by the stream
-// alone.  The host formulas (transformAssociateToMap, transformUpdate,
-// transformFusion, the keyframe decision) are in slio_lmap.cpp.
-struct slio_lmap {
-  slio_lmap_params prm{};
-  slio_handle h[4] = {nullptr, nullptr, nullptr, nullptr};
-  std::vector<float> poses6;   // cloudKeyPoses6D: {rx, ry, rz, tx, ty, tz} per key
-  bool coeff_ok[2] = {false, false};
-};
-
-static int lmap_check(slio_lmap_handle m, const char* who) {
-  if (!m) {
-    set_error(std::string(who) + ": null mapper");
-    return SLIO_EINVAL;
-  }
-  return SLIO_OK;
-}
-
-// VoxelGrid of n device points (float4 xyzi) into handle c's scan
-static int lmap_voxel4(Ctx& c, const float4* src, int64_t n, float leaf, int64_t* n_down) {
-  float *dx_ = nullptr, *dy_ = nullptr, *dz_ = nullptr;
-  if (n > 0) {
-    hipError_t e;
-    if ((e = MapDev::take(c.pre[0], 12 * n))) {
-      set_error(std::string("slio_lmap_feed: hipMalloc: ") + hipGetErrorString(e));
-      return SLIO_ENOMEM;
-    }
-    dx_ = (float*)c.pre[0].p;
-    dy_ = dx_ + n;
-    dz_ = dx_ + 2 * n;
-    k_lmap_split4<<<grid_blocks(n), 256, 0, c.stream>>>(src, n, dx_, dy_, dz_);
-    SLIO_HIP(hipGetLastError());
-  }
-  return voxel_device(c, dx_, dy_, dz_, n, leaf, n_down);
-}
-
-// downsampleCurrentScan (:1197-1220) from three device clouds
-static int lmap_feed_dev(slio_lmap* m, const float4* corner, int64_t nc, const float4* surf, int64_t ns,
-                         const float4* outlier, int64_t no, int64_t counts[4]) {
-  m->coeff_ok[0] = m->coeff_ok[1] = false;
-  int64_t k[4] = {0, 0, 0, 0};
-  Ctx& cc = m->h[SLIO_LMAP_CORNER]->c;
-  Ctx& ct = m->h[SLIO_LMAP_SURF_TOTAL]->c;
-  Ctx& cs = m->h[SLIO_LMAP_SURF]->c;
-  Ctx& co = m->h[SLIO_LMAP_OUTLIER]->c;
-  if (int rc = lmap_voxel4(cc, corner, nc, m->prm.leaf_corner, &k[0])) return rc;
-  if (int rc = lmap_voxel4(cs, surf, ns, m->prm.leaf_surf, &k[2])) return rc;
-  if (int rc = lmap_voxel4(co, outlier, no, m->prm.leaf_outlier, &k[3])) return rc;
-  // laserCloudSurfTotalLast = surfLastDS ++ outlierLastDS (:1215-1216), then
-  // downSizeFilterSurf again (:1217-1218)
-  const int64_t nt = k[2] + k[3];
-  float *tx = nullptr, *ty = nullptr, *tz = nullptr;
-  if (nt > 0) {
-    hipError_t e;
-    if ((e = MapDev::take(ct.pre[0], 12 * nt))) {
-      set_error(std::string("slio_lmap_feed: hipMalloc: ") + hipGetErrorString(e));
-      return SLIO_ENOMEM;
-    }
-    tx = (float*)ct.pre[0].p;
-    ty = tx + nt;
-    tz = tx + 2 * nt;
-    const Ctx* src[2] = {&cs, &co};
-    int64_t o = 0;
-    for (const Ctx* s : src) {
-      if (s->n == 0) continue;
-      SLIO_HIP(hipMemcpyAsync(tx + o, s->bx, 4 * s->n, hipMemcpyDeviceToDevice, ct.stream));
-      SLIO_HIP(hipMemcpyAsync(ty + o, s->by, 4 * s->n, hipMemcpyDeviceToDevice, ct.stream));
-      SLIO_HIP(hipMemcpyAsync(tz + o, s->bz, 4 * s->n, hipMemcpyDeviceToDevice, ct.stream));
-      o += s->n;
-    }
-  }
-  if (int rc = voxel_device(ct, tx, ty, tz, nt, m->prm.leaf_surf, &k[1])) return rc;
-  if (counts)
-    for (int i = 0; i < 4; ++i) counts[i] = k[i];
-  return SLIO_OK;
-}
-
-// one kind's transform, search and coefficient + rows launch, enqueued
-static int lmap_coeffs_enqueue(slio_lmap* m, int kind, const float transform[6]) {
-  Ctx& c = m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL]->c;
-  const int64_t n = c.n;
-  if (!c.wbx) {
-    const int64_t cap = c.prm.max_points;
-    hipError_t e;
-    if ((e = hipMalloc(&c.wbx, 4 * cap)) || (e = hipMalloc(&c.wby, 4 * cap)) || (e = hipMalloc(&c.wbz, 4 * cap))) {
-      set_error(std::string("slio_lmap_coeffs: hipMalloc: ") + hipGetErrorString(e));
-      return SLIO_ENOMEM;
-    }
-  }
-  if (n > 0) {
-    k_lmap_transform<<<grid_blocks(n), 256, 0, c.stream>>>(c.bx, c.by, c.bz, n, lmap_rot(transform), c.wbx, c.wby,
-                                                           c.wbz);
-    // the 5-NN of the map-frame points: the search pass in kNN-only mode with
-    // the identity pose, as slio_s2m_coeffs runs it
-    slio_pose idp{};
-    idp.rot[0] = 1.0;
-    idp.rli[0] = 1.0;
-    const PoseDev P = make_pose(&idp);
-    const ScanDev sd{c.wbx, c.wby, c.wbz, n};
-    if (int rc = enqueue_pass(c, &P, nullptr, 1, 0, nullptr, false, true, &sd)) return rc;
-    std::shared_lock<std::shared_mutex> lk(c.map->mu);
-    if (int rc = map_read_sync(c)) return rc;
-    // LMOptimization's trig, from transformTobeMapped[0..2] as written (:1457-1462)
-    S2mTrig T;
-    auto fc = [](float a) { return (float)std::cos((double)a); };
-    auto fs = [](float a) { return (float)std::sin((double)a); };
-    T.srx = fs(transform[0]), T.crx = fc(transform[0]);
-    T.sry = fs(transform[1]), T.cry = fc(transform[1]);
-    T.srz = fs(transform[2]), T.crz = fc(transform[2]);
-    const int nb = (int)((n + 255) / 256);
-    if (kind == 0)
-      k_lmap_coeff<0><<<nb, 256, 0, c.stream>>>(c.bx, c.by, c.bz, c.wbx, c.wby, c.wbz, n, c.nbr_pos, c.nbr_sqd,
-                                                c.map->pts, c.plane, c.sel, T, c.chunk_part);
-    else
-      k_lmap_coeff<1><<<nb, 256, 0, c.stream>>>(c.bx, c.by, c.bz, c.wbx, c.wby, c.wbz, n, c.nbr_pos, c.nbr_sqd,
-                                                c.map->pts, c.plane, c.sel, T, c.chunk_part);
-    SLIO_HIP(hipGetLastError());
-  }
-  c.s2m_kind = kind;
-  m->coeff_ok[kind] = true;
-  return SLIO_OK;
-}
-
-// the two kinds' partials summed in the fixed order (corners, then surfs)
-static int lmap_sum(slio_lmap* m, float AtA[36], float AtB[6], int64_t* nsel) {
-  double acc[kS2mSums] = {0};
-  for (int kind = 0; kind < 2; ++kind) {
-    Ctx& c = m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL]->c;
-    if (c.n == 0) continue;
-    const int nb = (int)((c.n + 255) / 256);
-    std::vector<double> part((size_t)nb * kS2mSums);
-    const Rb rb{part.data(), c.chunk_part, 8 * part.size()};
-    SLIO_HIP(readback(c.stream, &rb, 1));
-    for (int b = 0; b < nb; ++b)
-      for (int k = 0; k < kS2mSums; ++k) acc[k] = acc[k] + part[(size_t)b * kS2mSums + k];
-  }
-  int q = 0;
-  for (int r = 0; r < 6; ++r)
-    for (int cc = r; cc < 6; ++cc, ++q) AtA[6 * r + cc] = AtA[6 * cc + r] = (float)acc[q];
-  for (int r = 0; r < 6; ++r) AtB[r] = (float)acc[21 + r];
-  if (nsel) *nsel = (int64_t)llround(acc[27]);
-  return SLIO_OK;
-}
-
-static int lmap_coeff_state(slio_lmap* m, int kind, const char* who) {
-  Ctx& c = m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL]->c;
-  if (!c.map || !c.bx) {
-    set_error(std::string(who) + ": map and scan needed");
-    return SLIO_ESTATE;
-  }
-  return SLIO_OK;
-}
-
-extern "C" {
-
-int slio_lmap_params_default(slio_lmap_params* p) {
-  if (!p) {
-    set_error("slio_lmap_params_default: null");
-    return SLIO_EINVAL;
-  }
-  std::memset(p, 0, sizeof(*p));
-  p->device = 0;
-  p->max_points = 100000;
-  p->leaf_corner = 0.2f;
-  p->leaf_surf = 0.4f;
-  p->leaf_outlier = 0.4f;
-  p->pose_leaf = 1.0f;
-  p->search_radius = 50.0f;
-  p->max_iterations = 10;
-  p->mapping_interval = 0.3f;
-  p->scan_period = 0.1f;
-  p->keyframe_distance = 0.3f;
-  p->grid_cell = 0.0f;
-  return SLIO_OK;
-}
-
-int slio_lmap_destroy(slio_lmap_handle m) {
-  if (!m) return SLIO_OK;
-  int rc = SLIO_OK;
-  // (handle 0 owns the stream the others borrow: destroyed last)
-  for (int i = 3; i >= 0; --i)
-    if (m->h[i]) {
-      if (i > 0) (void)slio_set_stream(m->h[i], nullptr);
-      const int r = slio_destroy(m->h[i]);
-      if (r && !rc) rc = r;
-    }
-  delete m;
-  return rc;
-}
-
-int slio_lmap_create(slio_lmap_handle* out, const slio_lmap_params* p) {
-  if (!out || !p) {
-    set_error("slio_lmap_create: null argument");
-    return SLIO_EINVAL;
-  }
-  *out = nullptr;
-  if (p->max_points < 1 || !(p->leaf_corner > 0.0f) || !(p->leaf_surf > 0.0f) || !(p->leaf_outlier > 0.0f) ||
-      p->max_iterations < 0 || p->device < 0 || !(p->grid_cell >= 0.0f)) {
-    set_error("slio_lmap_create: bad max_points / leaves / max_iterations / device / grid_cell");
-    return SLIO_EINVAL;
-  }
-  auto* m = new slio_lmap();
-  m->prm = *p;
-  slio_params sp;
-  slio_params_default(&sp);
-  sp.device = p->device;
-  sp.max_points = p->max_points;
-  sp.grid_cell = p->grid_cell;
-  for (int i = 0; i < 4; ++i) {
-    int rc = slio_create(&m->h[i], &sp);
-    if (!rc && i > 0) rc = slio_set_stream(m->h[i], (void*)m->h[0]->c.stream);
-    if (!rc) rc = ensure_scan_buffers(m->h[i]->c);
-    if (rc) {
-      (void)slio_lmap_destroy(m);
-      return rc;
-    }
-  }
-  *out = m;
-  return SLIO_OK;
-}
-
-int slio_lmap_get_handle(slio_lmap_handle m, int which, slio_handle* out) {
-  if (int rc = lmap_check(m, "slio_lmap_get_handle")) return rc;
-  if (which < 0 || which > 3 || !out) {
-    set_error("slio_lmap_get_handle: bad arguments");
-    return SLIO_EINVAL;
-  }
-  // the caller may upload a scan or a map through it: nothing cached here survives that
-  m->coeff_ok[0] = m->coeff_ok[1] = false;
-  *out = m->h[which];
-  return SLIO_OK;
-}
-
-int slio_lmap_feed_lego(slio_lmap_handle m, void* lego, int64_t counts[4]) {
-  if (int rc = lmap_check(m, "slio_lmap_feed_lego")) return rc;
-  if (!lego) {
-    set_error("slio_lmap_feed_lego: null front-end handle");
-    return SLIO_EINVAL;
-  }
-  slio_lego_last_view v;
-  if (int rc = slio_lego_odom_last_view((slio_lego_handle)lego, &v)) return rc;
-  if (!v.published) {
-    set_error("slio_lmap_feed_lego: the last odometry call did not publish");
-    return SLIO_ESTATE;
-  }
-  if (v.device != m->prm.device) {
-    set_error("slio_lmap_feed_lego: the front-end is on another device");
-    return SLIO_EINVAL;
-  }
-  SLIO_HIP(hipSetDevice(m->prm.device));
-  return lmap_feed_dev(m, (const float4*)v.corner_xyzi, v.n_corner, (const float4*)v.surf_xyzi, v.n_surf,
-                       (const float4*)v.outlier_xyzi, v.n_outlier, counts);
-}
-
-int slio_lmap_feed_host(slio_lmap_handle m, const float* corner_xyzi, int64_t n_corner, const float* surf_xyzi,
-                        int64_t n_surf, const float* outlier_xyzi, int64_t n_outlier, int64_t counts[4]) {
-  if (int rc = lmap_check(m, "slio_lmap_feed_host")) return rc;
-  const float* src[3] = {corner_xyzi, surf_xyzi, outlier_xyzi};
-  const int64_t n[3] = {n_corner, n_surf, n_outlier};
-  for (int i = 0; i < 3; ++i)
-    if (n[i] < 0 || (n[i] > 0 && !src[i]) || n[i] > INT32_MAX) {
-      set_error("slio_lmap_feed_host: bad arguments");
-      return SLIO_EINVAL;
-    }
-  SLIO_HIP(hipSetDevice(m->prm.device));
-  // staged in the surf-total handle's temporaries (its own VoxelGrid runs last
-  // and uses pre[0] and pre[8..])
-  Ctx& ct = m->h[SLIO_LMAP_SURF_TOTAL]->c;
-  float4* d[3] = {nullptr, nullptr, nullptr};
-  for (int i = 0; i < 3; ++i) {
-    if (n[i] == 0) continue;
-    hipError_t e;
-    if ((e = MapDev::take(ct.pre[1 + i], 16 * n[i]))) {
-      set_error(std::string("slio_lmap_feed_host: hipMalloc: ") + hipGetErrorString(e));
-      return SLIO_ENOMEM;
-    }
-    d[i] = (float4*)ct.pre[1 + i].p;
-    SLIO_HIP(hipMemcpyAsync(d[i], src[i], 16 * n[i], hipMemcpyHostToDevice, ct.stream));
-  }
-  return lmap_feed_dev(m, d[0], n[0], d[1], n[1], d[2], n[2], counts);
-}
-
-int slio_lmap_extract(slio_lmap_handle m, const int32_t* key_ind, int32_t nsel, int64_t counts[4]) {
-  static const char* who = "slio_lmap_extract";
-  if (int rc = lmap_check(m, who)) return rc;
-  if (nsel < 0 || (nsel > 0 && !key_ind)) {
-    set_error("slio_lmap_extract: bad arguments");
-    return SLIO_EINVAL;
-  }
-  Ctx& cc = m->h[SLIO_LMAP_CORNER]->c;
-  Ctx& ct = m->h[SLIO_LMAP_SURF_TOTAL]->c;
-  const int32_t nkeys = (int32_t)(m->poses6.size() / 6);
-  std::vector<float> poses((size_t)nsel * 6);
-  for (int32_t i = 0; i < nsel; ++i) {
-    if (key_ind[i] < 0 || key_ind[i] >= nkeys) {
-      set_error("slio_lmap_extract: key index " + std::to_string(key_ind[i]) + " out of range");
-      return SLIO_EINVAL;
-    }
-    std::memcpy(&poses[6 * (size_t)i], &m->poses6[6 * (size_t)key_ind[i]], 24);
-  }
-  std::vector<KfSeg> segc, segs;
-  int64_t nc = 0, ns = 0;
-  const Ctx* srcc[1] = {&cc};
-  const Ctx* srcs[2] = {&m->h[SLIO_LMAP_SURF]->c, &m->h[SLIO_LMAP_OUTLIER]->c};
-  if (int rc = kf_segments(srcc, 1, key_ind, poses.data(), nsel, segc, nc, who, 1)) return rc;
-  if (int rc = kf_segments(srcs, 2, key_ind, poses.data(), nsel, segs, ns, who, 1)) return rc;
-  SLIO_HIP(hipSetDevice(m->prm.device));
-  m->coeff_ok[0] = m->coeff_ok[1] = false;
-  int64_t k[4] = {0, 0, 0, 0};
-  if (int rc = kf_assemble(cc, segc, nc, m->prm.leaf_corner, false, k, who, 1)) return rc;
-  if (int rc = kf_assemble(ct, segs, ns, m->prm.leaf_surf, false, k + 2, who, 1)) return rc;
-  if (counts)
-    for (int i = 0; i < 4; ++i) counts[i] = k[i];
-  return SLIO_OK;
-}
-
-int slio_lmap_coeffs(slio_lmap_handle m, int kind, const float transform[6], int64_t* nsel) {
-  if (int rc = lmap_check(m, "slio_lmap_coeffs")) return rc;
-  if ((kind != 0 && kind != 1) || !transform) {
-    set_error("slio_lmap_coeffs: bad arguments");
-    return SLIO_EINVAL;
-  }
-  if (int rc = lmap_coeff_state(m, kind, "slio_lmap_coeffs")) return rc;
-  SLIO_HIP(hipSetDevice(m->prm.device));
-  if (int rc = lmap_coeffs_enqueue(m, kind, transform)) return rc;
-  if (nsel) {
-    Ctx& c = m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL]->c;
-    std::vector<uint8_t> sl((size_t)c.n);
-    if (c.n) {
-      SLIO_HIP(hipStreamSynchronize(c.stream));
-      SLIO_HIP(hipMemcpy(sl.data(), c.sel, c.n, hipMemcpyDeviceToHost));
-    }
-    int64_t k = 0;
-    for (uint8_t v : sl) k += v;
-    *nsel = k;
-  }
-  return SLIO_OK;
-}
-
-int slio_lmap_get_coeffs(slio_lmap_handle m, int kind, float* coeff, uint8_t* sel) {
-  if (int rc = lmap_check(m, "slio_lmap_get_coeffs")) return rc;
-  if (kind != 0 && kind != 1) {
-    set_error("slio_lmap_get_coeffs: bad arguments");
-    return SLIO_EINVAL;
-  }
-  if (!m->coeff_ok[kind]) {
-    set_error("slio_lmap_get_coeffs: no coefficients of that kind");
-    return SLIO_ESTATE;
-  }
-  return slio_s2m_get_coeffs(m->h[kind == 0 ? SLIO_LMAP_CORNER : SLIO_LMAP_SURF_TOTAL], coeff, sel);
-}
-
-int slio_lmap_normal_equations(slio_lmap_handle m, float AtA[36], float AtB[6], int64_t* nsel) {
-  if (int rc = lmap_check(m, "slio_lmap_normal_equations")) return rc;
-  if (!AtA || !AtB) {
-    set_error("slio_lmap_normal_equations: bad arguments");
-    return SLIO_EINVAL;
-  }
-  if (!m->coeff_ok[0] || !m->coeff_ok[1]) {
-    set_error("slio_lmap_normal_equations: slio_lmap_coeffs of both kinds first");
-    return SLIO_ESTATE;
-  }
-  SLIO_HIP(hipSetDevice(m->prm.device));
-  return lmap_sum(m, AtA, AtB, nsel);
-}
-
-int slio_lmap_optimize(slio_lmap_handle m, float transform[6], int32_t* iterations, int32_t* is_degenerate) {
-  if (int rc = lmap_check(m, "slio_lmap_optimize")) return rc;
-  if (!transform || !iterations || !is_degenerate) {
-    set_error("slio_lmap_optimize: bad arguments");
-    return SLIO_EINVAL;
-  }
-  for (int kind = 0; kind < 2; ++kind)
-    if (int rc = lmap_coeff_state(m, kind, "slio_lmap_optimize")) return rc;
-  *iterations = 0;
-  *is_degenerate = 0;
-  // :1606
-  if (!(m->h[SLIO_LMAP_CORNER]->c.map->n > 10 && m->h[SLIO_LMAP_SURF_TOTAL]->c.map->n > 100)) return SLIO_OK;
-  SLIO_HIP(hipSetDevice(m->prm.device));
-  float matP[36] = {0};
-  int deg = 0;
-  for (int it = 0; it < m->prm.max_iterations; ++it) {
-    if (int rc = lmap_coeffs_enqueue(m, 0, transform)) return rc;
-    if (int rc = lmap_coeffs_enqueue(m, 1, transform)) return rc;
-    float AtA[36], AtB[6];
-    int64_t nsel = 0;
-    if (int rc = lmap_sum(m, AtA, AtB, &nsel)) return rc;
-    int conv = 0;
-    const int rc = slio_s2m_lm_step(AtA, AtB, nsel, it, transform, &deg, matP, &conv);
-    if (rc < 0) return rc;
-    *iterations = it + 1;
-    if (conv) break;
-  }
-  *is_degenerate = deg;
-  return SLIO_OK;
-}
-
-int slio_lmap_save_keyframe(slio_lmap_handle m, const float pose6[6], int32_t* key) {
-  if (int rc = lmap_check(m, "slio_lmap_save_keyframe")) return rc;
-  if (!pose6) {
-    set_error("slio_lmap_save_keyframe: null pose");
-    return SLIO_EINVAL;
-  }
-  const int which[3] = {SLIO_LMAP_CORNER, SLIO_LMAP_SURF, SLIO_LMAP_OUTLIER};
-  int32_t k = -1;
-  for (int w : which) {
-    int32_t kk = -1;
-    if (int rc = slio_s2m_kf_push_scan(m->h[w], &kk)) return rc;
-    k = kk;
-  }
-  m->poses6.insert(m->poses6.end(), pose6, pose6 + 6);
-  if (key) *key = k;
-  return SLIO_OK;
-}
-
-int slio_lmap_get_key_poses(slio_lmap_handle m, float* poses6, int32_t cap, int32_t* nkeys) {
-  if (int rc = lmap_check(m, "slio_lmap_get_key_poses")) return rc;
-  const int32_t nk = (int32_t)(m->poses6.size() / 6);
-  if (nkeys) *nkeys = nk;
-  if (poses6) {
-    if (cap < nk) {
-      set_error("slio_lmap_get_key_poses: buffer too small");
-      return SLIO_ECAPACITY;
-    }
-    if (nk) std::memcpy(poses6, m->poses6.data(), sizeof(float) * m->poses6.size());
-  }
-  return SLIO_OK;
-}
-
-int slio_lmap_clear(slio_lmap_handle m) {
-  if (int rc = lmap_check(m, "slio_lmap_clear")) return rc;
-  const int which[3] = {SLIO_LMAP_CORNER, SLIO_LMAP_SURF, SLIO_LMAP_OUTLIER};
-  for (int w : which)
-    if (int rc = slio_s2m_kf_clear(m->h[w])) return rc;
-  m->poses6.clear();
-  m->coeff_ok[0] = m->coeff_ok[1] = false;
-  return SLIO_OK;
-}
-
-}  // extern "C"
 
 namespace slio {
 

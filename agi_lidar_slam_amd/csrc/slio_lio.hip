@@ -90,8 +90,7 @@ struct Deskew {
 };
 
 // ---------------------------------------------------------------- math
-__device__ __forceinline__ float fcos(float a) { return (float)cos((double)a); }
-__device__ __forceinline__ float fsin(float a) { return (float)sin((double)a); }
+// (fsin / fcos: slio_common.hpp)
 __device__ __forceinline__ float fatan2(float y, float x) { return (float)atan2((double)y, (double)x); }
 
 struct Aff {
@@ -3738,8 +3737,7 @@ int slio_lego_create(slio_lego_handle* out, const slio_lego_params* p) {
   h->g = LGeo{p->n_scan, p->horizon_scan, p->ground_scan_ind, p->segment_valid_point_num,
               p->segment_valid_line_num, p->ang_res_x, p->ang_res_y, p->ang_bottom,
               p->sensor_mount_angle, p->segment_theta,
-              (float)std::sin((double)ax), (float)std::cos((double)ax),
-              (float)std::sin((double)ay), (float)std::cos((double)ay), h->cells};
+              fsin(ax), fcos(ax), fsin(ay), fcos(ay), h->cells};
   const int64_t C = h->cells, N = h->cap, R = p->n_scan;
   hipError_t e = hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking);
   h->stream = h->own;

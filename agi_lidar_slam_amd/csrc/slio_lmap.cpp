@@ -22,8 +22,8 @@ using slio::set_error;
 
 namespace {
 
-inline float fsin(float a) { return (float)std::sin((double)a); }
-inline float fcos(float a) { return (float)std::cos((double)a); }
+using slio::fcos;
+using slio::fsin;
 inline float fasin(float a) { return (float)std::asin((double)a); }
 inline float fatan2(float y, float x) { return (float)std::atan2((double)y, (double)x); }
 

@@ -12,7 +12,7 @@ mkdir -p $out ${OUT:-agi_lidar_slam_amd/_abl}
 tag=$(python3 -c "from agi_lidar_slam_amd import build; print(build.source_hash())")
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -DSLIO_SOURCE_HASH=\"$tag\" -Iinclude $*"
 pids=()
-for s in slio_device.hip slio_ikf.cpp slio_imu.cpp slio_s2m.cpp slio_lio.hip slio_lego_odom.hip slio_lmap.cpp; do
+for s in $(python3 -c "from agi_lidar_slam_amd import build; print(' '.join(build.SOURCES))"); do
   /opt/rocm/bin/hipcc $F -c agi_lidar_slam_amd/csrc/$s -o $out/$s.o 2>$out/$s.err & pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done

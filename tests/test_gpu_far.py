@@ -3,7 +3,7 @@
 A scan point whose 5-NN the fine grid cannot finish -- 5th neighbour beyond
 the 5x5x5 fine cube, query cell more than 2 cells outside the grid -- is
 deferred to the end of its workgroup's kNN phase and answered by a whole
-wavefront on the coarse level (slio_device.hip, far_search).  ikd-Tree has no
+wavefront on the coarse level (slio_search.hpp, far_search).  ikd-Tree has no
 such split (ikd_Tree.cpp:960-1101 visits the tree the same way for every
 query), so the bar is the same as for every other query: indices and squared
 distances bit-exact vs the oracle's ikd-Tree restatement.
