@@ -214,6 +214,12 @@ class SlioLegoLastView(C.Structure):
                 ("published", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SlioLvxParams(C.Structure):
+    """slio_lvx_params (include/slio.h)."""
+    _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("leaf_corner", C.c_float),
+                ("leaf_surf", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
 class SlioLmapParams(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("leaf_corner", C.c_float),
                 ("leaf_surf", C.c_float), ("leaf_outlier", C.c_float), ("pose_leaf", C.c_float),
@@ -373,6 +379,30 @@ SIGNATURES = {
     "slio_lmap_fuse": (C.c_int, [C.POINTER(SlioLmapFusion), _FP, _FP, _FP]),
     "slio_lmap_keyframe_decision": (C.c_int, [_FP, _FP, C.c_int32, C.c_double, _IP]),
     "slio_lmap_qr_solve": (C.c_int, [C.c_int, C.c_int, _FP, _FP, _FP]),
+    "slio_lvx_params_default": (C.c_int, [C.POINTER(SlioLvxParams)]),
+    "slio_lvx_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioLvxParams)]),
+    "slio_lvx_destroy": (C.c_int, [_P]),
+    "slio_lvx_clear": (C.c_int, [_P]),
+    "slio_lvx_select_cubes": (C.c_int, [_P, _FP, _IP, _IP, _IP, _IP, _IP]),
+    "slio_lvx_update_map": (C.c_int, [_P, _FP, _FP, C.c_int64, _FP, C.c_int64, _IP, C.c_int32, _I64P]),
+    "slio_lvx_cube_sizes": (C.c_int, [_P, C.c_int, _IP]),
+    "slio_lvx_get_cube": (C.c_int, [_P, C.c_int, C.c_int32, _FP, C.c_int64, _I64P]),
+    "slio_lvx_get_surround": (C.c_int, [_P, C.c_int, _IP, C.c_int32, _FP, C.c_int64, _I64P]),
+    "slio_lvx_get_centers": (C.c_int, [_P, _IP]),
+    "slio_lvx_feed_host": (C.c_int, [_P, _FP, C.c_int64, _FP, C.c_int64, _I64P]),
+    "slio_lvx_get_scan": (C.c_int, [_P, C.c_int, _FP, C.c_int64, _I64P]),
+    "slio_lvx_build_maps": (C.c_int, [_P, _IP, C.c_int32, _I64P]),
+    "slio_lvx_pass": (C.c_int, [_P, C.c_int, _FP, _I64P]),
+    "slio_lvx_get_pass": (C.c_int, [_P, C.c_int, _FP, _IP, _FP, _FP, _U8P]),
+    "slio_lvx_normal_equations": (C.c_int, [_P, _FP, _FP, _I64P]),
+    "slio_lvx_optimize": (C.c_int, [_P, _FP, _IP, _IP]),
+    "slio_lvx_process": (C.c_int, [_P, _FP, C.c_int64, _FP, C.c_int64, _FP, _IP]),
+    "slio_lvx_get_transforms": (C.c_int, [_P, _FP, _FP, _FP]),
+    "slio_lvx_set_transform": (C.c_int, [_P, _FP]),
+    "slio_lvx_cube_index": (C.c_int, [C.c_float, C.c_int32, _IP]),
+    "slio_lvx_select_host": (C.c_int, [_FP, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
+    "slio_lvx_plane_solve": (C.c_int, [_FP, C.c_int, _FP]),
+    "slio_lvx_lm_step": (C.c_int, [_FP, _FP, C.c_int64, C.c_int, _FP, C.POINTER(C.c_int), _FP, C.POINTER(C.c_int)]),
 }
 
 _lib = None

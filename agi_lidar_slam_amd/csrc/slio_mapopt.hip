@@ -21,6 +21,7 @@
 #include "slio_cvsolve.hpp"
 #include "slio_device.hpp"
 #include "slio_frontend.h"
+#include "slio_livox.hpp"
 #include "slio_plane.hpp"
 
 using namespace slio;
@@ -403,6 +404,165 @@ __global__ __launch_bounds__(256) void k_lmap_coeff(
 }
 
 // float4 xyzi (the front-end's clouds) -> SoA, for the VoxelGrid
+// ---- livox_mapping laserMapping (livox_mapping/src/laserMapping.cpp) --------
+// A sorted list of the K smallest 64-bit keys (bits(d^2) << 32) | position:
+// totally ordered, so the result does not depend on the order of insertion
+// (ties at equal float distance go to the lower position in the cell-sorted
+// map).  A sibling of Top5 for K = 5 and 8; insertion is a compare-exchange
+// chain without data-dependent branches.
+template <int K>
+struct TopK {
+  uint64_t k[K];
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int j = 0; j < K; ++j) k[j] = ~0ull;
+  }
+  __device__ __forceinline__ void insert(uint64_t key) {
+    k[K - 1] = key < k[K - 1] ? key : k[K - 1];
+#pragma unroll
+    for (int j = K - 1; j > 0; --j) {
+      const uint64_t lo = k[j] < k[j - 1] ? k[j] : k[j - 1], hi = k[j] < k[j - 1] ? k[j - 1] : k[j];
+      k[j - 1] = lo;
+      k[j] = hi;
+    }
+  }
+};
+
+// surfOptimization after the plane solve on EIGHT neighbours (:977-1026):
+// s2m_surf_coeff's arithmetic (the `break` of :1000 changes no result)
+__device__ __forceinline__ uint8_t lvx_surf_coeff(const float (&sol)[3], const float (&nb)[8][3], float x0, float y0,
+                                                  float z0, float4& cf) {
+  uint8_t ok = 0;
+  float pa = sol[0], pb = sol[1], pc = sol[2], pd = 1;
+  const float ps = sqrtf(pa * pa + pb * pb + pc * pc);
+  pa /= ps;
+  pb /= ps;
+  pc /= ps;
+  pd /= ps;
+  bool valid = true;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (fabsf(pa * nb[j][0] + pb * nb[j][1] + pc * nb[j][2] + pd) > 0.2) valid = false;
+  if (valid) {
+    const float pd2 = pa * x0 + pb * y0 + pc * z0 + pd;
+    const float s = 1 - 0.9 * fabsf(pd2) / sqrtf(sqrtf(x0 * x0 + y0 * y0 + z0 * z0));
+    cf = make_float4(s * pa, s * pb, s * pc, s * pd2);
+    ok = s > 0.1;
+  }
+  return ok;
+}
+
+// One pass of the optimisation loop for one class (:825-950 corner, :954-1028
+// surf) and its rows (:1059-1095, which read beside s2m_lm_rot are the same
+// expressions in the same order), one thread per scan point:
+// pointAssociateToMap, the exact K-NN, the gate, the coefficient, the row, and
+// the 28 fp64 sums of the workgroup as k_lmap_coeff leaves them.
+//
+// Exactness of the K-NN without refinement.  The query lies in the centre cell
+// of its 3 x 3 x 3 block of cells of edge h, so every map point outside the
+// block is at least `bound` away, bound = the query's distance to the nearest
+// face of the block less kCellTol (the float rounding of the cell function is
+// ~3e-5 m at 300 m), and bound >= h - kCellTol > sqrt(gate) (h = 1.25 against
+// sqrt(1.5) = 1.2247, 2.25 against sqrt(5) = 2.2361).  If the K-th distance
+// inside the block is <= bound, the block's K nearest are the map's.  If not,
+// the map's K-th distance is > sqrt(gate) whichever points it is made of, and
+// the reference drops the query at :833 / :961.  A query whose cell is not in
+// 1 .. n - 2 of an axis is a full cell away from every map point (the grid
+// has two cells of padding): dropped the same way, nothing is read.  Nobody
+// waits on anybody.  A query that is not proven, or that the gate rejects,
+// leaves index -1 and distance +inf.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_lvx_pass(const slio::lvx::GridView g, const float* __restrict__ body,
+                                                  int64_t n, LegoRot T, S2mTrig trig, slio::lvx::PassOut o) {
+  constexpr int K = KIND == 0 ? 5 : 8;
+  constexpr float kGate = KIND == 0 ? 1.5f : 5.0f;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double v[kS2mSums];
+#pragma unroll
+  for (int k = 0; k < kS2mSums; ++k) v[k] = 0.0;
+  if (i < n) {
+    const float bx = body[3 * i], by = body[3 * i + 1], bz = body[3 * i + 2];
+    float w[3];
+    lego_to_map(T, bx, by, bz, w[0], w[1], w[2]);
+    o.world[3 * i] = w[0];
+    o.world[3 * i + 1] = w[1];
+    o.world[3 * i + 2] = w[2];
+    TopK<K> top;
+    top.init();
+    bool near = false;
+    if (g.n > 0) {
+      const int dim[3] = {g.nx, g.ny, g.nz};
+      int c[3];
+      bool inside = true;
+      float bound = g.h;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const float fc = floorf((w[a] - g.o[a]) * g.inv_h);
+        inside = inside && fc >= 1.0f && fc <= (float)(dim[a] - 2);  // (false for NaN)
+        c[a] = (int)fminf(fmaxf(fc, 1.0f), (float)(dim[a] - 2));
+        bound = fminf(bound, w[a] - (g.o[a] + (float)(c[a] - 1) * g.h));
+        bound = fminf(bound, (g.o[a] + (float)(c[a] + 2) * g.h) - w[a]);
+      }
+      bound -= slio::lvx::kCellTol;
+      if (inside) {
+        for (int dz = -1; dz <= 1; ++dz)
+          for (int dy = -1; dy <= 1; ++dy) {
+            const int64_t base = ((int64_t)(c[2] + dz) * g.ny + (c[1] + dy)) * g.nx + (c[0] - 1);
+            const uint32_t p0 = g.start[base], p1 = g.start[base + 3];
+            for (uint32_t p = p0; p < p1; ++p) {
+              const float4 q = g.pts[p];
+              const float dx = q.x - w[0], dy2 = q.y - w[1], dz2 = q.z - w[2];
+              const float d2 = (dx * dx + dy2 * dy2) + dz2 * dz2;
+              top.insert(((uint64_t)__float_as_uint(d2) << 32) | p);
+            }
+          }
+        const uint64_t kth = top.k[K - 1];
+        const float d2k = __uint_as_float((uint32_t)(kth >> 32));
+        near = kth != ~0ull && bound > 0.0f && d2k <= bound * bound && d2k < kGate;
+      }
+    }
+    uint8_t ok = 0;
+    float4 cf = make_float4(0, 0, 0, 0);
+    if (near) {
+      float nb[K][3];
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const float4 q = g.pts[(uint32_t)top.k[j]];
+        nb[j][0] = q.x;
+        nb[j][1] = q.y;
+        nb[j][2] = q.z;
+        o.nbr_idx[i * K + j] = (int32_t)__float_as_uint(q.w);
+        o.nbr_sqd[i * K + j] = __uint_as_float((uint32_t)(top.k[j] >> 32));
+      }
+      if constexpr (KIND == 0) {
+        ok = s2m_corner_coeff(nb, w[0], w[1], w[2], cf);
+      } else {
+        // matA0 is 10 x 3 with two zero rows against -1 (:423-425); the 8 x 3
+        // system gives the same bits (slio_lvx_plane_solve).  A failed solve
+        // leaves x = 0: ps = 0, NaNs, `s > 0.1` false.
+        const float m1[8] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f};
+        float sol[3];
+        if (!slio::cvs::qr_solve_mn<8, 3>(&nb[0][0], m1, sol)) sol[0] = sol[1] = sol[2] = 0.0f;
+        ok = lvx_surf_coeff(sol, nb, w[0], w[1], w[2], cf);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        o.nbr_idx[i * K + j] = -1;
+        o.nbr_sqd[i * K + j] = INFINITY;
+      }
+    }
+    o.coeff[i] = cf;
+    o.sel[i] = ok;
+    if (ok) {
+      const S2mRot r = s2m_lm_rot(trig, bx, by, bz, cf.x, cf.y, cf.z);
+      const float a[6] = {r.arx, r.ary, r.arz, cf.x, cf.y, cf.z};
+      s2m_products(a, -cf.w, v);
+    }
+  }
+  block_sums_256(v, o.partial);
+}
+
 __global__ void k_lmap_split4(const float4* __restrict__ in, int64_t n, float* __restrict__ x,
                               float* __restrict__ y, float* __restrict__ z) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -435,6 +595,20 @@ static Aff12 s2m_affine(const float tf[6]) {
 // LMOptimization's trig of the three angles (float sin / cos)
 static S2mTrig s2m_trig(float rx, float ry, float rz) {
   return S2mTrig{fsin(rx), fcos(rx), fsin(ry), fcos(ry), fsin(rz), fcos(rz)};
+}
+
+int slio::lvx::pass_launch(int kind, const GridView& g, const float* body_xyz, int64_t n, const float tf[6],
+                           const PassOut& out, hipStream_t st) {
+  if (n == 0) return SLIO_OK;
+  const LegoRot T = lmap_rot(tf);
+  const S2mTrig trig = s2m_trig(tf[0], tf[1], tf[2]);
+  const int nb = (int)((n + 255) / 256);
+  if (kind == 0)
+    k_lvx_pass<0><<<nb, 256, 0, st>>>(g, body_xyz, n, T, trig, out);
+  else
+    k_lvx_pass<1><<<nb, 256, 0, st>>>(g, body_xyz, n, T, trig, out);
+  SLIO_HIP(hipGetLastError());
+  return SLIO_OK;
 }
 
 // The scan of c in the map frame and its 5-NN: to_map() launches the kernel

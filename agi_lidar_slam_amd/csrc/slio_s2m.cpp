@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstring>
 
+#include <string>
 #include <utility>
 
 #include "slio_common.hpp"
@@ -23,10 +24,16 @@ using slio::cvs::inv_lu;
 using slio::cvs::jacobi;
 using slio::cvs::qr_solve;
 
-extern "C" int slio_s2m_lm_step(const float AtA[36], const float AtB[6], int64_t nsel, int iter_count,
-                                float transform[6], int* is_degenerate, float matP[36], int* converged) {
+// The step LIO-SAM's LMOptimization, LeGO-LOAM's (mapOptmization.cpp:1539-1600)
+// and livox_mapping's laserMapping (:1040-1150) share.  They differ in the
+// eigenvalue threshold of the degeneracy test (100, 100, 1) and in deltaR:
+// pcl::rad2deg(float) is a float product, livox_mapping's own rad2deg (:139)
+// a double expression (deg_double).
+static int lm_step(const char* who, const float AtA[36], const float AtB[6], int64_t nsel, int iter_count,
+                   float transform[6], int* is_degenerate, float matP[36], int* converged, float eig_threshold,
+                   bool deg_double) {
   if (!AtA || !AtB || !transform || !is_degenerate || !matP || !converged) {
-    set_error("slio_s2m_lm_step: bad arguments");
+    set_error(std::string(who) + ": bad arguments");
     return SLIO_EINVAL;
   }
   *converged = 0;
@@ -39,14 +46,14 @@ extern "C" int slio_s2m_lm_step(const float AtA[36], const float AtB[6], int64_t
     for (float& v : X) v = 0.0f;
   if (iter_count == 0) {
     // :1633-1656: eigen-decomposition of A^T A; directions with eigenvalue
-    // < 100 (smallest first) are not updated
+    // below the threshold (100; smallest first) are not updated
     float A[36], E[6], V[36], V2[36];
     std::memcpy(A, AtA, sizeof A);
     jacobi<6>(A, E, V);
     std::memcpy(V2, V, sizeof V);
     *is_degenerate = 0;
     for (int i = 5; i >= 0; --i) {
-      if (E[i] < 100.0f) {
+      if (E[i] < eig_threshold) {
         for (int j = 0; j < 6; ++j) V2[6 * i + j] = 0;
         *is_degenerate = 1;
       } else {
@@ -55,7 +62,7 @@ extern "C" int slio_s2m_lm_step(const float AtA[36], const float AtB[6], int64_t
     }
     float Vi[36];
     if (!inv_lu<6>(V, Vi)) {
-      set_error("slio_s2m_lm_step: singular eigenvector matrix");
+      set_error(std::string(who) + ": singular eigenvector matrix");
       return SLIO_EINVAL;
     }
     for (int i = 0; i < 6; ++i)
@@ -76,10 +83,32 @@ extern "C" int slio_s2m_lm_step(const float AtA[36], const float AtB[6], int64_t
   }
   for (int k = 0; k < 6; ++k) transform[k] += X[k];
   const float r2d = (float)(180.0 / M_PI);
-  const float deltaR = std::sqrt(std::pow(X[0] * r2d, 2) + std::pow(X[1] * r2d, 2) + std::pow(X[2] * r2d, 2));
+  float deltaR;
+  if (deg_double) {
+    auto deg = [](float r) { return (double)r * 180.0 / M_PI; };
+    deltaR = std::sqrt(std::pow(deg(X[0]), 2) + std::pow(deg(X[1]), 2) + std::pow(deg(X[2]), 2));
+  } else {
+    deltaR = std::sqrt(std::pow(X[0] * r2d, 2) + std::pow(X[1] * r2d, 2) + std::pow(X[2] * r2d, 2));
+  }
   const float deltaT = std::sqrt(std::pow(X[3] * 100, 2) + std::pow(X[4] * 100, 2) + std::pow(X[5] * 100, 2));
   *converged = (deltaR < 0.05 && deltaT < 0.05) ? 1 : 0;
   return SLIO_OK;
+}
+
+extern "C" int slio_s2m_lm_step(const float AtA[36], const float AtB[6], int64_t nsel, int iter_count,
+                                float transform[6], int* is_degenerate, float matP[36], int* converged) {
+  return lm_step("slio_s2m_lm_step", AtA, AtB, nsel, iter_count, transform, is_degenerate, matP, converged, 100.0f,
+                 false);
+}
+
+// livox_mapping's step (laserMapping.cpp:1040-1150): eignThre = 1 (:1114), and
+// fewer than 50 rows is a `continue` (:1040-1042) -- the turn counts and
+// nothing moves, which is what the return value 1 already means to a caller's
+// loop.
+extern "C" int slio_lvx_lm_step(const float AtA[36], const float AtB[6], int64_t nsel, int iter_count,
+                                float transform[6], int* is_degenerate, float matP[36], int* converged) {
+  return lm_step("slio_lvx_lm_step", AtA, AtB, nsel, iter_count, transform, is_degenerate, matP, converged, 1.0f,
+                 true);
 }
 
 // LeGO-LOAM's calculateTransformationSurf / Corner after the normal equations

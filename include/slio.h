@@ -768,6 +768,187 @@ int slio_lmap_keyframe_decision(const float prev_pos[3], const float cur_pos[3],
  * (6, 6)}; returns 1 where the solve gives up (x zeroed). */
 int slio_lmap_qr_solve(int m, int n, const float* A, const float* b, float* x);
 
+/* ---- livox_mapping laserMapping (src/livox_mapping/src/laserMapping.cpp): the
+ *      rolling cube map, its host formulas and the Gauss-Newton step -----------
+ * All path:line below are in that file.  laserCloudCornerArray /
+ * laserCloudSurfArray are 21 x 11 x 21 cubes of 50 m (:64-72), cube index
+ * i + 21 j + 231 k; kind 0 is the corner class, kind 1 the surf class.  One
+ * opaque handle owns both classes on one device and one stream.  For every
+ * class and cube the device holds exactly the ordered cloud the reference holds
+ * in laserCloud*Array[ind] after the same calls; slio_lvx_get_cube and
+ * slio_lvx_cube_sizes show it.  Poses are {rx, ry, rz, tx, ty, tz}
+ * (transformTobeMapped's layout), clouds n x {x, y, z} float32; the intensity
+ * is not stored (nothing up to :1246 reads it).
+ *
+ * Errors: SLIO_OK or a negative SLIO_E* with slio_last_error() set.  Argument
+ * errors (null pointers, negative sizes, a kind outside {0, 1}, a cube outside
+ * 0 .. 4850, a pose that is not finite) are reported before any device call.
+ *
+ * slio_lvx_process is one call of the node's main loop (:475-1216); the other
+ * entries are its stages, for tests and for users who drive them themselves.
+ *
+ * Stated departures from the reference:
+ *  - k-NN ties at equal float distance go to the lower position in the
+ *    cell-sorted map, where FLANN's order is not pinned by anything;
+ *  - neighbour lists of points the gate rejects are not produced;
+ *  - inside a voxel the points are summed in ascending position of the input
+ *    (slio_scan_upload_voxel's VoxelGrid semantics; the stored points of a cube
+ *    come before the appended ones), where PCL's std::sort leaves it open;
+ *  - sin / cos / sqrt of a float are the double functions (rounded to float
+ *    where the reference assigns to one);
+ *  - a point whose map-frame coordinates are not finite, or beyond 1e6 m, is
+ *    dropped at append: the reference converts it with int(), which is
+ *    undefined (x86-64 gives INT_MIN: out of range, dropped as well). */
+typedef struct slio_lvx* slio_lvx_handle;
+#define SLIO_LVX_CUBES 4851 /* laserCloudNum (:71-72) */
+typedef struct slio_lvx_params {
+  int32_t device;
+  int32_t max_points; /* capacity of each class: stored plus incoming points */
+  float leaf_corner;  /* filter_parameter_corner: 0.2 (horizon, outdoor), 0.1 (mid) */
+  float leaf_surf;    /* filter_parameter_surf: 0.4 / 0.2                            */
+  int32_t reserved[4];
+} slio_lvx_params;
+int slio_lvx_params_default(slio_lvx_params* p);
+/* EINVAL: max_points < 1, a leaf that is not positive and finite, no such
+ * device.  No leaf can overflow the VoxelGrid's sort key: a voxel index stays
+ * below 2^31 by PCL's own rule, under which a leaf too small for a cube's
+ * extent passes that cube through unfiltered. */
+int slio_lvx_create(slio_lvx_handle* out, const slio_lvx_params* p);
+int slio_lvx_destroy(slio_lvx_handle m);
+/* Empty both classes; laserCloudCenWidth / Height / Depth back to 10 / 5 / 10. */
+int slio_lvx_clear(slio_lvx_handle m);
+/* :475-776 at transformTobeMapped = transform: pointOnYAxis, the centre cube,
+ * the six shift loops (the handle mirrors laserCloudCen*; several shifts in
+ * one call compose as the reference's do, and each class's points are
+ * relabelled and re-sorted on the device in one pass with one host wait; no
+ * shift, no device work), then the cubes centre +- 2 in i, j, k order: every
+ * one inside the array is a surround cube (laserCloudSurroundInd), those with
+ * a corner inside the field of view (:727-761) are valid (laserCloudValidInd).
+ * The handle keeps both lists for slio_lvx_update_map / slio_lvx_get_surround.
+ * center[3] = centerCubeI / J / K after the shifts; valid / surround hold up to
+ * 125 entries; any output may be NULL. */
+int slio_lvx_select_cubes(slio_lvx_handle m, const float transform[6], int32_t center[3],
+                          int32_t* valid, int32_t* nvalid, int32_t* surround, int32_t* nsurround);
+/* :1159-1216 at transformTobeMapped = transform: every point of corner_xyz (the
+ * raw laserCloudCornerLast) and of surf_xyz (laserCloudSurfLast_down) goes
+ * through pointAssociateToMap (:195-217: yaw about z, roll about x, pitch
+ * about y in float, then the translation), its cube index comes from the
+ * double arithmetic of :1162-1168, and it is appended to that cube if the cube
+ * is inside the array, valid or not.  Then every listed cube of both classes is
+ * replaced by its VoxelGrid (leaf_corner / leaf_surf), each under
+ * slio_scan_upload_voxel's semantics applied to that cube's cloud alone: its
+ * own bounding box, min_b and div_b, the leaf-too-small pass-through, sums in
+ * ascending input position, output in voxel-index order.  Every listed cube
+ * is filtered on every call, whether it received a point or not, as the
+ * reference does.  valid == NULL (nvalid 0): the list of the last
+ * slio_lvx_select_cubes (ESTATE without one).  The scans are the only points
+ * that cross PCIe; the host waits once per class (the new total and the 4852
+ * offsets).  counts = the classes' new totals (may be NULL).  ECAPACITY when
+ * stored + incoming points of a class exceed max_points. */
+int slio_lvx_update_map(slio_lvx_handle m, const float transform[6], const float* corner_xyz,
+                        int64_t n_corner, const float* surf_xyz, int64_t n_surf,
+                        const int32_t* valid, int32_t nvalid, int64_t counts[2]);
+/* laserCloud{Corner,Surf}Array[ind]->size() for ind = 0 .. 4850 (host table). */
+int slio_lvx_cube_sizes(slio_lvx_handle m, int kind, int32_t sizes[SLIO_LVX_CUBES]);
+/* laserCloud{Corner,Surf}Array[cube] to the host: *n points (n may be NULL);
+ * xyz may be NULL (size only); ECAPACITY when cap < *n. */
+int slio_lvx_get_cube(slio_lvx_handle m, int kind, int32_t cube, float* xyz, int64_t cap, int64_t* n);
+/* laserCloudSurround2_corner (kind 0) / laserCloudSurround2 (kind 1), :1218-1224:
+ * the concatenation of the listed cubes (at most 125) in list order, gathered
+ * on the device and downloaded.  cubes == NULL (ncubes 0): the surround list
+ * of the last slio_lvx_select_cubes (ESTATE without one). */
+int slio_lvx_get_surround(slio_lvx_handle m, int kind, const int32_t* cubes, int32_t ncubes,
+                          float* xyz, int64_t cap, int64_t* n);
+/* laserCloudCenWidth / Height / Depth. */
+int slio_lvx_get_centers(slio_lvx_handle m, int32_t cen[3]);
+/* The two scans of a call (:351-369 and :789-798): corner_xyz = the raw
+ * laserCloudCornerLast, kept as it is (the corner branch runs over it, :825);
+ * surf_xyz = laserCloudSurfLast, which goes through downSizeFilterSurf
+ * (leaf_surf, slio_scan_upload_voxel's semantics) on the device into
+ * laserCloudSurfLast_down.  counts = {corner points, surf points after the
+ * grid}.  The only input path so far; one host wait (the grid's count) and one
+ * at the end, after which the host clouds have been read.  ECAPACITY: a scan
+ * larger than max_points. */
+int slio_lvx_feed_host(slio_lvx_handle m, const float* corner_xyz, int64_t n_corner,
+                       const float* surf_xyz, int64_t n_surf, int64_t counts[2]);
+/* The fed scan of a kind (kind 1: laserCloudSurfLast_down); xyz may be NULL. */
+int slio_lvx_get_scan(slio_lvx_handle m, int kind, float* xyz, int64_t cap, int64_t* n);
+/* :778-787 and the two setInputCloud of :816-817: laserCloud*FromMap = the valid
+ * cubes of the last slio_lvx_select_cubes in laserCloudValidInd order, and over
+ * each a search grid (cells of 1.25 m corner / 2.25 m surf, cell-sorted points,
+ * offsets).  counts = the two maps' sizes.  One host wait per class (the map's
+ * bounding box).  valid == NULL (nvalid 0): the list of the last
+ * slio_lvx_select_cubes (ESTATE without one); ECAPACITY when the valid cubes
+ * span more than 2^24 cells.  A map update or a new selection invalidates it. */
+int slio_lvx_build_maps(slio_lvx_handle m, const int32_t* valid, int32_t nvalid, int64_t counts[2]);
+/* One class's turn of the loop (:825-950 corner, kind 0; :954-1028 surf, kind 1)
+ * at transformTobeMapped = transform, with its rows (:1059-1095) and their fp64
+ * sums per workgroup, in ONE launch: pointAssociateToMap, the exact 5-NN / 8-NN
+ * in the map (gate sqd[4] < 1.5 / sqd[7] < 5.0), the line through +- 0.1 of the
+ * first eigenvector with D[0] > 3 D[1] (cv::eigen as slio_cvsolve.hpp restates
+ * it) or the plane of slio_lvx_plane_solve with all eight neighbours within
+ * 0.2, s > 0.1.  A failed plane solve leaves x = 0, the NaNs that follow
+ * unselect the point.  nsel may be NULL (no wait then).  ESTATE: no map built
+ * or no scan fed.
+ * Departures: ties of the K-NN at equal float distance go to the lower
+ * position in the cell-sorted map; the neighbour lists of points the gate
+ * rejects are not produced (index -1, distance +inf). */
+int slio_lvx_pass(slio_lvx_handle m, int kind, const float transform[6], int64_t* nsel);
+/* What the last slio_lvx_pass of a kind left, n = that scan's size: world n x 3
+ * (pointSel), nbr_idx / nbr_sqd n x 5 (kind 0) or n x 8 (kind 1) with indices
+ * into laserCloud*FromMap, coeff n x 4, sel n.  Any output may be NULL. */
+int slio_lvx_get_pass(slio_lvx_handle m, int kind, float* world, int32_t* nbr_idx, float* nbr_sqd,
+                      float* coeff, uint8_t* sel);
+/* A^T A / A^T B (:1099-1101) of the rows the last slio_lvx_pass of BOTH kinds
+ * left: fp64 sums in k_lmap_coeff's fixed tree (slio_lmap_normal_equations),
+ * corners before surfs, rounded to float.  One host wait. */
+int slio_lvx_normal_equations(slio_lvx_handle m, float AtA[36], float AtB[6], int64_t* nsel);
+/* :814-1151: only with more than 10 corner and more than 100 surf map points
+ * (else *iterations = 0, transform untouched); at most 20 turns of pass(0),
+ * pass(1), the normal equations (the turn's one host wait) and
+ * slio_lvx_lm_step.  isDegenerate and matP persist across calls in the handle
+ * as the node's globals do.  *iterations = num_temp. */
+int slio_lvx_optimize(slio_lvx_handle m, float transform[6], int32_t* iterations,
+                      int32_t* is_degenerate);
+/* One call of the main loop, :475-1216: select_cubes at the handle's
+ * transformTobeMapped (what the previous call left: transformAssociateToMap is
+ * commented out at :472), build_maps, feed_host, optimize, transformUpdate
+ * (:188-193, only when the loop ran), and the map update from the fed scans on
+ * the device.  Host waits: 2 (maps) + 2 (feed) + 1 per turn + 2 (update), + 2
+ * when the map shifts.  transform_aft_mapped and iterations may be NULL. */
+int slio_lvx_process(slio_lvx_handle m, const float* corner_xyz, int64_t n_corner,
+                     const float* surf_xyz, int64_t n_surf, float transform_aft_mapped[6],
+                     int32_t* iterations);
+/* transformTobeMapped / transformAftMapped / transformLastMapped; any may be NULL. */
+int slio_lvx_get_transforms(slio_lvx_handle m, float tobe_mapped[6], float aft_mapped[6],
+                            float last_mapped[6]);
+/* Set transformTobeMapped (an initial guess from outside the node). */
+int slio_lvx_set_transform(slio_lvx_handle m, const float tobe_mapped[6]);
+/* -- host only, callable without a GPU -- */
+/* int((t + 25.0) / 50.0) + cen, one less when t + 25.0 < 0 (:482-491,
+ * :1162-1168).  EINVAL for a t that is not finite or beyond 1e6 m. */
+int slio_lvx_cube_index(float t, int32_t cen, int32_t* cube);
+/* slio_lvx_select_cubes without a handle: cen[3] (laserCloudCen*) in and out,
+ * shift[3] = how many cubes the contents move along i, j, k (+1 per turn of a
+ * `while (centerCube < 3)` loop, -1 per turn of the opposite one). */
+int slio_lvx_select_host(const float transform[6], int32_t cen[3], int32_t center[3],
+                         int32_t shift[3], int32_t* valid, int32_t* nvalid, int32_t* surround,
+                         int32_t* nsurround);
+/* The plane system of the surf branch (:962-975): cv::solve(DECOMP_QR) of
+ * matA0 x = matB0 as slio_cvsolve.hpp restates it, nb_xyz = the 8 neighbours.
+ * m = 10 is the reference's system (10 x 3, rows 8 and 9 zero, against ten
+ * times -1); m = 8 leaves the zero rows out and gives the same bits: a zero row
+ * adds +0 to every column norm and dot product of the Householder steps and the
+ * back-substitution reads the top three rows only.  Returns 1 where the solve
+ * gives up (x zeroed). */
+int slio_lvx_plane_solve(const float* nb_xyz, int m, float x[3]);
+/* The step after the normal equations (:1102-1150): slio_s2m_lm_step's body
+ * with eignThre = 1 (:1114) and deltaR from the file's own double rad2deg
+ * (:139).  Returns 1 (nothing done, *converged = 0) with fewer than 50 rows:
+ * the reference's `continue` (:1040-1042), a turn that still counts. */
+int slio_lvx_lm_step(const float AtA[36], const float AtB[6], int64_t nsel, int iter_count,
+                     float transform[6], int* is_degenerate, float matP[36], int* converged);
+
 /* Manifold helpers exported for tests (esekfom.hpp:59-73, 236-258). */
 int slio_state_boxplus(const slio_state* x, const double dx[24], slio_state* out);
 int slio_state_boxminus(const slio_state* x1, const slio_state* x2, double dx[24]);

@@ -21,6 +21,11 @@
             odometry on the same sequence: ms per mapping call and its split,
             iterations, map sizes, the host restatement beside it (only when
             named)
+  livox_map livox_mapping's laserMapping (LivoxMapping: slio_lvx_*) on a synthetic
+            Avia-pattern trajectory with crude feature clouds: ms per mapping
+            call and its split (select + gather, downsample, optimise, update),
+            iterations, map and cube sizes, host waits, the last call once more
+            through the host restatement (only when named)
 One JSON line per measurement (host wall clock around synchronous calls)."""
 import ctypes as C
 import json
@@ -528,8 +533,109 @@ def lego_map(calls=8, restate=True):
     fe.close()
 
 
+def livox_map(calls=12, n_scan=20000):
+    """livox_mapping's laserMapping (LivoxMapping: slio_lvx_*) on
+    synth.make_trajectory's Avia frames, 0.3 m apart.  Feature clouds, crude,
+    from what the scene knows (as make_s2m_problem makes them): corner = points
+    on the buildings' vertical edges within 40 m of the sensor, surf = the whole
+    frame.  One mapper runs `process` per frame (ms per mapping call); a second
+    one runs the same calls stage by stage for the split (select + gather and
+    index, downsample, optimise, update -- its update re-uploads the scans, so
+    the split's sum is above the one-call figure).  The map frame is the first
+    frame's.  The first call apart (no map yet, and it allocates); the last
+    call once more through tests/livox_map_model.py (numpy, the oracle's
+    kd-tree and VoxelGrid) from a copy of the map as it stood."""
+    import livox_map_model as M
+    from oracle import oracle as O
+    from agi_lidar_slam_amd import synth
+    from agi_lidar_slam_amd.livox_map import LivoxMapping
+    O.build()
+    seed, n_map = 20261015, 200000
+    frames = synth.make_trajectory(seed, n_map, calls, n_scan, step=0.3)
+    scene = synth.make_scene(seed, n_map)
+    rng = np.random.default_rng(4)
+    lines = []
+    for bx in scene.boxes:
+        for (cx, cy) in ((bx[0], bx[1]), (bx[2], bx[1]), (bx[0], bx[3]), (bx[2], bx[3])):
+            z = np.arange(0.0, bx[5], 0.1)
+            lines.append(np.stack([cx + rng.normal(0, 0.005, z.size), cy + rng.normal(0, 0.005, z.size), z], 1))
+    edges = np.concatenate(lines)
+
+    def knn(kind, mp, world):
+        k = M.KNN[kind]
+        if len(mp) < k or len(world) == 0:
+            return np.zeros((len(world), 0), np.int32), np.zeros((len(world), 0), np.float32)
+        return O.Tree(mp).knn(world, k)
+
+    dev, lock = LivoxMapping(), LivoxMapping()
+    model = M.Mapper(O.voxel_grid, knn)
+    rows, host = [], None
+    tobe = np.zeros(6, np.float32)
+    for k, fr in enumerate(frames):
+        R = synth.quat_matrix(fr.gt_rot)
+        t = fr.gt_pos + R @ synth.AVIA_T_LI
+        near = edges[np.linalg.norm(edges[:, :2] - t[:2], axis=1) < 40][::3]
+        corner = ((near + rng.normal(0, 0.01, near.shape) - t) @ R).astype(np.float32)
+        surf = np.ascontiguousarray(fr.body, np.float32)
+        last = k == len(frames) - 1
+        if last:
+            # the model catches up with the device map and pose as they stand (untimed)
+            for kind in range(2):
+                sz = dev.cube_sizes(kind)
+                model.cubes[kind] = {int(i): dev.get_cube(kind, int(i)) for i in np.nonzero(sz)[0]}
+            model.cen = [int(v) for v in dev.laserCloudCen]
+            model.tobe[:], model.aft[:], model.last[:] = dev._transforms()
+        t0 = time.perf_counter()
+        dev.process(corner, surf)
+        t1 = time.perf_counter()
+        # the same call in stages
+        _, valid, _ = lock.select_cubes(tobe)
+        maps = lock.build_maps()
+        s1 = time.perf_counter()
+        scans = lock.feed_host(corner, surf)
+        s2 = time.perf_counter()
+        tobe, iters, _ = lock.optimize(tobe)
+        s3 = time.perf_counter()
+        totals = lock.update_map(tobe, lock.scan(0), lock.scan(1))
+        s4 = time.perf_counter()
+        sizes = [dev.cube_sizes(kind) for kind in range(2)]
+        rows.append(dict(ms_call=(t1 - t0) * 1e3, ms_select_gather=(s1 - t1) * 1e3, ms_downsample=(s2 - s1) * 1e3,
+                         ms_optimise=(s3 - s2) * 1e3, ms_update_staged=(s4 - s3) * 1e3, iterations=dev.iterations,
+                         same_pose_staged=bool(np.array_equal(tobe, dev.transformTobeMapped)),
+                         scan_corner_surf_down=[int(v) for v in scans], map_searched=[int(v) for v in maps],
+                         map_total=[int(v) for v in totals], valid_cubes=len(valid),
+                         nonempty_cubes=[int((sz > 0).sum()) for sz in sizes],
+                         largest_cube=[int(sz.max()) for sz in sizes]))
+        if last:
+            h0 = time.perf_counter()
+            it_m = model.process(corner, surf)
+            h1 = time.perf_counter()
+            host = dict(ms_call=(h1 - h0) * 1e3, iterations=it_m,
+                        same_bits_as_device=bool(np.array_equal(model.tobe, dev.transformTobeMapped)
+                                                 and all(np.array_equal(model.sizes(kd), dev.cube_sizes(kd))
+                                                         for kd in range(2))))
+    later = rows[1:]
+    mean = lambda key: float(np.mean([r[key] for r in later]))  # noqa: E731
+    R = synth.quat_matrix(frames[0].gt_rot)
+    t_first = frames[0].gt_pos + R @ synth.AVIA_T_LI
+    t_last = frames[-1].gt_pos + synth.quat_matrix(frames[-1].gt_rot) @ synth.AVIA_T_LI
+    moved = float(np.linalg.norm(t_last - t_first))
+    print(json.dumps({
+        "bench": "livox_map", "pattern": "avia", "n_scan": n_scan, "calls": len(rows), "first_call": rows[0],
+        "mean_after_first": {key: mean(key) for key in ("ms_call", "ms_select_gather", "ms_downsample",
+                                                        "ms_optimise", "ms_update_staged", "iterations")},
+        "last_call": rows[-1], "host_restatement_last_call": host,
+        "true_distance_moved": moved, "estimated_distance_moved": float(np.linalg.norm(dev.transformTobeMapped[3:])),
+        "host_waits_per_call": "2 maps + 2 feed + 1 per iteration + 2 update (+ 2 when the map shifts)",
+        "kernel_times": "not measured"}), flush=True)
+    dev.close()
+    lock.close()
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "livox_map" in what:
+        livox_map()
     if "lego_map" in what:
         lego_map()
     if "lego_odom" in what:
