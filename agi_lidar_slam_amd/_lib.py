@@ -220,6 +220,11 @@ class SlioLvxParams(C.Structure):
                 ("leaf_surf", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
+class SlioLregParams(C.Structure):
+    """slio_lreg_params (include/slio_frontend.h)."""
+    _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 class SlioLmapParams(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("leaf_corner", C.c_float),
                 ("leaf_surf", C.c_float), ("leaf_outlier", C.c_float), ("pose_leaf", C.c_float),
@@ -403,6 +408,18 @@ SIGNATURES = {
     "slio_lvx_select_host": (C.c_int, [_FP, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
     "slio_lvx_plane_solve": (C.c_int, [_FP, C.c_int, _FP]),
     "slio_lvx_lm_step": (C.c_int, [_FP, _FP, C.c_int64, C.c_int, _FP, C.POINTER(C.c_int), _FP, C.POINTER(C.c_int)]),
+    "slio_lvx_feed_device": (C.c_int, [_P, _P, _I64P]),
+    "slio_lvx_process_cloud": (C.c_int, [_P, _P, _FP, C.c_int64, _FP, _IP, _IP]),
+    "slio_lreg_params_default": (C.c_int, [C.POINTER(SlioLregParams)]),
+    "slio_lreg_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioLregParams)]),
+    "slio_lreg_destroy": (C.c_int, [_P]),
+    "slio_lreg_run": (C.c_int, [_P, _FP, C.c_int64, _IP]),
+    "slio_lreg_get_cloud": (C.c_int, [_P, _FP, C.c_int64]),
+    "slio_lreg_get_features": (C.c_int, [_P, C.c_int, _FP, C.c_int64]),
+    "slio_lreg_get_flags": (C.c_int, [_P, _IP, _U8P]),
+    "slio_lreg_chain_tile": (C.c_int, [_IP, _IP]),
+    "slio_lreg_classify_host": (C.c_int, [_FP, C.c_int64, _IP, _U8P, _FP, _FP, _FP, _IP, _IP]),
+    "slio_lreg_plane_judge": (C.c_int, [_FP, C.c_int32, C.c_int32, _IP]),
 }
 
 _lib = None

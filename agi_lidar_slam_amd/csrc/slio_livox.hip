@@ -37,7 +37,9 @@
 #include <vector>
 
 #include "slio_device.hpp"
+#include "slio_frontend.h"
 #include "slio_livox.hpp"
+#include "slio_lreg.hpp"
 
 using slio::set_error;
 using slio::MapDev;
@@ -971,6 +973,73 @@ int sum_partials(slio_lvx* m, float AtA[36], float AtB[6], int64_t* nsel) {
   return SLIO_OK;
 }
 
+// n x {x, y, z, intensity} on the device -> n x {x, y, z}
+__global__ void k_lvx_take_xyz(const float* __restrict__ in, int64_t n, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[3 * i] = in[4 * i];
+  out[3 * i + 1] = in[4 * i + 1];
+  out[3 * i + 2] = in[4 * i + 2];
+}
+
+// A feed is feed_begin, then the caller's copies on the stream -- the corner
+// cloud into scan[0].xyz, the surf cloud into m->in, both n x 3, from the host
+// (slio_lvx_feed_host) or from the registration's clouds (slio_lvx_feed_device)
+// -- then feed_finish, the part both share.
+int feed_begin(slio_lvx* m, int64_t n_corner, int64_t n_surf, const char* who) {
+  if (n_corner > m->prm.max_points || n_surf > m->prm.max_points) {
+    set_error(std::string(who) + ": scan exceeds max_points");
+    return SLIO_ECAPACITY;
+  }
+  SLIO_HIP(hipSetDevice(m->prm.device));
+  for (int k = 0; k < 2; ++k) m->scan[k].fed = m->scan[k].passed = false;
+  hipError_t e = hipSuccess;
+  if (n_corner) e = MapDev::take(m->scan[0].xyz, 12 * (size_t)n_corner);
+  if (!e && n_surf) e = MapDev::take(m->in, 12 * (size_t)n_surf);
+  if (e) {
+    set_error(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+    return SLIO_ENOMEM;
+  }
+  return SLIO_OK;
+}
+
+int feed_finish(slio_lvx* m, int64_t n_corner, int64_t n_surf, int64_t counts[2], const char* who) {
+  hipStream_t st = m->stream;
+  // corner: the raw laserCloudCornerLast (:825 runs over it, not over _down)
+  Scan& c0 = m->scan[0];
+  c0.n = n_corner;
+  // surf: downSizeFilterSurf (:795-798) = the per-cube VoxelGrid of a one-cube map
+  Scan& s1 = m->scan[1];
+  Class& tmp = m->cls[2];
+  tmp.cur = 0;
+  tmp.n = 0;
+  if (n_surf) {
+    k_lvx_scan_in<<<blocks(n_surf), 256, 0, st>>>((const float*)m->in.p, n_surf, tmp.xyz[0][0], tmp.xyz[0][1],
+                                                  tmp.xyz[0][2], tmp.id[0]);
+    const int32_t zero = 0;
+    int rc = upload_filter(m, &zero, 1);
+    if (!rc) rc = rebuild(m, 2, n_surf, true, m->prm.leaf_surf, who);
+    if (rc) return rc;
+    const int32_t cube0 = 0;
+    int64_t total = 0;
+    if ((rc = gather(m, 2, &cube0, 1, &total, &s1.xyz))) return rc;
+    s1.n = total;
+  } else {
+    s1.n = 0;
+  }
+  for (int k = 0; k < 2; ++k) {
+    if (m->scan[k].n)
+      if (int rc = take_scan_outputs(m, k, m->scan[k].n)) return rc;
+    m->scan[k].fed = true;
+  }
+  SLIO_HIP(hipStreamSynchronize(st));  // the source clouds have been read
+  if (counts) {
+    counts[0] = c0.n;
+    counts[1] = s1.n;
+  }
+  return SLIO_OK;
+}
+
 bool finite6(const float* t) {
   for (int a = 0; a < 6; ++a)
     if (!std::isfinite(t[a])) return false;
@@ -988,58 +1057,30 @@ int slio_lvx_feed_host(slio_lvx_handle m, const float* corner_xyz, int64_t n_cor
     set_error("slio_lvx_feed_host: bad arguments");
     return SLIO_EINVAL;
   }
-  if (n_corner > m->prm.max_points || n_surf > m->prm.max_points) {
-    set_error("slio_lvx_feed_host: scan exceeds max_points");
-    return SLIO_ECAPACITY;
+  if (int rc = feed_begin(m, n_corner, n_surf, "slio_lvx_feed_host")) return rc;
+  // the upload part: the two host clouds into the buffers the device part reads
+  if (n_corner)
+    SLIO_HIP(hipMemcpyAsync(m->scan[0].xyz.p, corner_xyz, 12 * (size_t)n_corner, hipMemcpyHostToDevice, m->stream));
+  if (n_surf) SLIO_HIP(hipMemcpyAsync(m->in.p, surf_xyz, 12 * (size_t)n_surf, hipMemcpyHostToDevice, m->stream));
+  return feed_finish(m, n_corner, n_surf, counts, "slio_lvx_feed_host");
+}
+
+int slio_lvx_feed_device(slio_lvx_handle m, void* reg, int64_t counts[2]) {
+  LVX_CHECK(m, "slio_lvx_feed_device");
+  slio::lreg::View v{};
+  if (int rc = slio::lreg::view(reg, &v, "slio_lvx_feed_device")) return rc;
+  if (v.device != m->prm.device) {
+    set_error("slio_lvx_feed_device: the registration and the mapper are on different devices");
+    return SLIO_EINVAL;
   }
-  SLIO_HIP(hipSetDevice(m->prm.device));
-  hipStream_t st = m->stream;
-  for (int k = 0; k < 2; ++k) m->scan[k].fed = m->scan[k].passed = false;
-  // corner: the raw laserCloudCornerLast (:825 runs over it, not over _down)
-  Scan& c0 = m->scan[0];
-  if (n_corner) {
-    if (hipError_t e = MapDev::take(c0.xyz, 12 * (size_t)n_corner)) {
-      set_error(std::string("slio_lvx_feed_host: hipMalloc: ") + hipGetErrorString(e));
-      return SLIO_ENOMEM;
-    }
-    SLIO_HIP(hipMemcpyAsync(c0.xyz.p, corner_xyz, 12 * (size_t)n_corner, hipMemcpyHostToDevice, st));
-  }
-  c0.n = n_corner;
-  // surf: downSizeFilterSurf (:795-798) = the per-cube VoxelGrid of a one-cube map
-  Scan& s1 = m->scan[1];
-  Class& tmp = m->cls[2];
-  tmp.cur = 0;
-  tmp.n = 0;
-  if (n_surf) {
-    if (hipError_t e = MapDev::take(m->in, 12 * (size_t)n_surf)) {
-      set_error(std::string("slio_lvx_feed_host: hipMalloc: ") + hipGetErrorString(e));
-      return SLIO_ENOMEM;
-    }
-    SLIO_HIP(hipMemcpyAsync(m->in.p, surf_xyz, 12 * (size_t)n_surf, hipMemcpyHostToDevice, st));
-    k_lvx_scan_in<<<blocks(n_surf), 256, 0, st>>>((const float*)m->in.p, n_surf, tmp.xyz[0][0], tmp.xyz[0][1],
-                                                  tmp.xyz[0][2], tmp.id[0]);
-    const int32_t zero = 0;
-    int rc = upload_filter(m, &zero, 1);
-    if (!rc) rc = rebuild(m, 2, n_surf, true, m->prm.leaf_surf, "slio_lvx_feed_host");
-    if (rc) return rc;
-    const int32_t cube0 = 0;
-    int64_t total = 0;
-    if ((rc = gather(m, 2, &cube0, 1, &total, &s1.xyz))) return rc;
-    s1.n = total;
-  } else {
-    s1.n = 0;
-  }
-  for (int k = 0; k < 2; ++k) {
-    if (m->scan[k].n)
-      if (int rc = take_scan_outputs(m, k, m->scan[k].n)) return rc;
-    m->scan[k].fed = true;
-  }
-  SLIO_HIP(hipStreamSynchronize(st));  // the host clouds have been read
-  if (counts) {
-    counts[0] = c0.n;
-    counts[1] = s1.n;
-  }
-  return SLIO_OK;
+  const int64_t n_corner = v.n_corner, n_surf = v.n_surf;
+  if (int rc = feed_begin(m, n_corner, n_surf, "slio_lvx_feed_device")) return rc;
+  // (slio_lreg_run ended with a wait: the registration's clouds are complete)
+  if (n_corner)
+    k_lvx_take_xyz<<<blocks(n_corner), 256, 0, m->stream>>>(v.corner_xyzi, n_corner, (float*)m->scan[0].xyz.p);
+  if (n_surf) k_lvx_take_xyz<<<blocks(n_surf), 256, 0, m->stream>>>(v.surf_xyzi, n_surf, (float*)m->in.p);
+  SLIO_HIP(hipGetLastError());
+  return feed_finish(m, n_corner, n_surf, counts, "slio_lvx_feed_device");
 }
 
 int slio_lvx_get_scan(slio_lvx_handle m, int kind, float* xyz, int64_t cap, int64_t* n) {
@@ -1189,16 +1230,16 @@ int slio_lvx_optimize(slio_lvx_handle m, float transform[6], int32_t* iterations
   return SLIO_OK;
 }
 
-int slio_lvx_process(slio_lvx_handle m, const float* corner_xyz, int64_t n_corner, const float* surf_xyz,
-                     int64_t n_surf, float transform_aft_mapped[6], int32_t* iterations) {
-  LVX_CHECK(m, "slio_lvx_process");
-  if (n_corner < 0 || n_surf < 0 || (n_corner && !corner_xyz) || (n_surf && !surf_xyz)) {
-    set_error("slio_lvx_process: bad arguments");
-    return SLIO_EINVAL;
-  }
+}  // extern "C"
+
+namespace {
+
+// One call of the main loop (:475-1216) around the given feed
+template <class Feed>
+int process_with(slio_lvx* m, Feed feed, float transform_aft_mapped[6], int32_t* iterations) {
   int rc = slio_lvx_select_cubes(m, m->tobe, nullptr, nullptr, nullptr, nullptr, nullptr);
   if (!rc) rc = slio_lvx_build_maps(m, nullptr, 0, nullptr);
-  if (!rc) rc = slio_lvx_feed_host(m, corner_xyz, n_corner, surf_xyz, n_surf, nullptr);
+  if (!rc) rc = feed();
   int32_t iters = 0;
   if (!rc) rc = slio_lvx_optimize(m, m->tobe, &iters, nullptr);
   if (rc) return rc;
@@ -1213,6 +1254,41 @@ int slio_lvx_process(slio_lvx_handle m, const float* corner_xyz, int64_t n_corne
   if (transform_aft_mapped) std::memcpy(transform_aft_mapped, m->aft, sizeof m->aft);
   if (iterations) *iterations = iters;
   return SLIO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slio_lvx_process(slio_lvx_handle m, const float* corner_xyz, int64_t n_corner, const float* surf_xyz,
+                     int64_t n_surf, float transform_aft_mapped[6], int32_t* iterations) {
+  LVX_CHECK(m, "slio_lvx_process");
+  if (n_corner < 0 || n_surf < 0 || (n_corner && !corner_xyz) || (n_surf && !surf_xyz)) {
+    set_error("slio_lvx_process: bad arguments");
+    return SLIO_EINVAL;
+  }
+  return process_with(
+      m, [&] { return slio_lvx_feed_host(m, corner_xyz, n_corner, surf_xyz, n_surf, nullptr); }, transform_aft_mapped,
+      iterations);
+}
+
+int slio_lvx_process_cloud(slio_lvx_handle m, void* reg, const float* xyzi, int64_t n, float transform_aft_mapped[6],
+                           int32_t* iterations, int32_t counts[3]) {
+  LVX_CHECK(m, "slio_lvx_process_cloud");
+  if (n < 0 || (n && !xyzi)) {
+    set_error("slio_lvx_process_cloud: negative size or null cloud");
+    return SLIO_EINVAL;
+  }
+  int32_t dev = -1;
+  if (int rc = slio::lreg::device_of(reg, &dev, "slio_lvx_process_cloud")) return rc;
+  if (dev != m->prm.device) {
+    set_error("slio_lvx_process_cloud: the registration and the mapper are on different devices");
+    return SLIO_EINVAL;
+  }
+  int32_t cnt[3] = {0, 0, 0};
+  if (int rc = slio_lreg_run((slio_lreg_handle)reg, xyzi, n, cnt)) return rc;
+  if (counts) std::memcpy(counts, cnt, sizeof cnt);
+  return process_with(m, [&] { return slio_lvx_feed_device(m, reg, nullptr); }, transform_aft_mapped, iterations);
 }
 
 int slio_lvx_get_transforms(slio_lvx_handle m, float tobe_mapped[6], float aft_mapped[6], float last_mapped[6]) {

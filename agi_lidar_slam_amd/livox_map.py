@@ -237,6 +237,28 @@ class LivoxMapping(LivoxCubeMap):
         self.scan_counts = counts
         return counts
 
+    def feed_device(self, reg):
+        """feed_host from the clouds the last run of ``reg`` (a
+        livox_reg.LivoxScanRegistration) left on the device: cornerPointsSharp
+        as it is, surfPointsFlat through downSizeFilterSurf; nothing crosses
+        PCIe.  Returns the two sizes."""
+        counts = np.zeros(2, np.int64)
+        L.check(self.lib.slio_lvx_feed_device(self.h, reg.h, L.i64ptr(counts)), "lvx_feed_device")
+        self.scan_counts = counts
+        return counts
+
+    def process_cloud(self, reg, cloud) -> np.ndarray:
+        """From the sensor's cloud (n, 4) to a pose: the registration on
+        ``reg``, then ``process`` with the device feed.  Returns
+        transformAftMapped; ``reg.counts`` holds the registration's sizes."""
+        c = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
+        aft, it, counts = np.zeros(6, np.float32), C.c_int32(), np.zeros(3, np.int32)
+        L.check(self.lib.slio_lvx_process_cloud(self.h, reg.h, L.fptr(c), c.shape[0], L.fptr(aft), C.byref(it),
+                                                L.iptr(counts)), "lvx_process_cloud")
+        self.iterations = it.value
+        reg.counts = counts
+        return aft
+
     def scan(self, kind: int) -> np.ndarray:
         n = C.c_int64()
         L.check(self.lib.slio_lvx_get_scan(self.h, kind, None, 0, C.byref(n)), "lvx_get_scan")

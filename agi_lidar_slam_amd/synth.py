@@ -443,3 +443,44 @@ def make_s2m_problem(seed: int = 20261015, n_map: int = 200000, n_surf: int = 20
     cw = cw + rng.normal(0, 0.01, cw.shape)
     corner_scan = ((cw - t) @ R).astype(np.float32)
     return dict(surf_map=surf_map, corner_map=corner_map, surf_scan=fr.body, corner_scan=corner_scan, tf=tf)
+
+
+# ---------------------------------------------------------------- a continuous scan curve
+STREET_FURNITURE = ((6.0, -1.6, 0.5, 1.2), (9.5, 1.9, 0.4, 2.4), (13.0, -0.8, 0.6, 1.0), (17.0, 1.1, 0.5, 3.0))
+"""(metres ahead, metres to the left, edge, height) of four small boxes in front of the sensor."""
+
+
+def with_street_furniture(scene: Scene, pos, yaw: float) -> Scene:
+    """The scene plus four small boxes 6-17 m ahead of a sensor at pos looking along yaw."""
+    c, s = np.cos(yaw), np.sin(yaw)
+    extra = []
+    for ahead, left, edge, h in STREET_FURNITURE:
+        cx, cy = pos[0] + c * ahead - s * left, pos[1] + s * ahead + c * left
+        extra.append([cx - edge / 2, cy - edge / 2, cx + edge / 2, cy + edge / 2, 0.0, h])
+    return Scene(half=scene.half, boxes=np.concatenate([scene.boxes, np.array(extra)]))
+
+
+def make_scan_curve(scene: Scene, pos, yaw: float, n_rays: int, k0: int = 0, seed: int = 0,
+                    noise: float = 0.002, max_range: float = 120.0, furniture: bool = True) -> np.ndarray:
+    """A scan as livox_mapping's scanRegistration expects it: returns in
+    firing order along ONE continuous curve (a Lissajous figure, az = 0.6
+    sin(0.003 i), el = -0.05 + 0.2 sin(0.0171 i): consecutive rays at most 0.2
+    degrees apart), N(0, noise) range noise, no voxel thinning, rays without a
+    return left out.  The Avia frames of make_frame are voxel-thinned and carry
+    no scan-line continuity.  Returns (n, 4) float32 {x, y, z, reflectivity} in
+    the LiDAR frame (x forward), n <= n_rays."""
+    pos = np.asarray(pos, np.float64)
+    sc = with_street_furniture(scene, pos, yaw) if furniture else scene
+    i = np.arange(k0, k0 + n_rays, dtype=np.float64)
+    az = 0.6 * np.sin(0.003 * i)
+    el = -0.05 + 0.2 * np.sin(0.0171 * i)
+    dl = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], 1)
+    R = quat_matrix(quat_from_rotvec(np.array([0.0, 0.0, yaw])))
+    dw = dl @ R.T
+    t = _cast(sc, pos, dw, max_range)
+    ok = np.isfinite(t)
+    rng = np.random.default_rng(seed + 31)
+    tt = t[ok] + rng.normal(0.0, noise, int(ok.sum()))
+    body = dl[ok] * tt[:, None]
+    refl = rng.integers(1, 200, int(ok.sum())).astype(np.float64)
+    return np.ascontiguousarray(np.concatenate([body, refl[:, None]], 1), dtype=np.float32)

@@ -866,11 +866,18 @@ int slio_lvx_get_centers(slio_lvx_handle m, int32_t cen[3]);
  * surf_xyz = laserCloudSurfLast, which goes through downSizeFilterSurf
  * (leaf_surf, slio_scan_upload_voxel's semantics) on the device into
  * laserCloudSurfLast_down.  counts = {corner points, surf points after the
- * grid}.  The only input path so far; one host wait (the grid's count) and one
- * at the end, after which the host clouds have been read.  ECAPACITY: a scan
- * larger than max_points. */
+ * grid}.  One host wait (the grid's count) and one at the end, after which the
+ * host clouds have been read.  ECAPACITY: a scan larger than max_points. */
 int slio_lvx_feed_host(slio_lvx_handle m, const float* corner_xyz, int64_t n_corner,
                        const float* surf_xyz, int64_t n_surf, int64_t counts[2]);
+/* The same feed, device to device, from the clouds the last slio_lreg_run of
+ * `reg` (a slio_lreg_handle, slio_frontend.h) left in HBM: cornerPointsSharp is
+ * the raw corner scan, surfPointsFlat goes through downSizeFilterSurf exactly
+ * as above.  x, y, z only (the mapper stores no intensity); no point crosses
+ * PCIe.  The upload is the only part the two feeds do not share, so equal
+ * clouds give equal scans.  EINVAL: a registration handle that is null or
+ * destroyed, or on another device; ESTATE: no run on it yet. */
+int slio_lvx_feed_device(slio_lvx_handle m, void* reg, int64_t counts[2]);
 /* The fed scan of a kind (kind 1: laserCloudSurfLast_down); xyz may be NULL. */
 int slio_lvx_get_scan(slio_lvx_handle m, int kind, float* xyz, int64_t cap, int64_t* n);
 /* :778-787 and the two setInputCloud of :816-817: laserCloud*FromMap = the valid
@@ -919,6 +926,15 @@ int slio_lvx_optimize(slio_lvx_handle m, float transform[6], int32_t* iterations
 int slio_lvx_process(slio_lvx_handle m, const float* corner_xyz, int64_t n_corner,
                      const float* surf_xyz, int64_t n_surf, float transform_aft_mapped[6],
                      int32_t* iterations);
+/* From the sensor's cloud to a pose: slio_lreg_run(reg, xyzi, n) (scanRegistration's
+ * laserCloudHandler, slio_frontend.h), then slio_lvx_process's body with
+ * slio_lvx_feed_device in place of the host feed.  Only the raw cloud crosses
+ * PCIe; host waits are those of slio_lvx_process plus one, the registration's
+ * counts.  counts = {laserCloud, cornerPointsSharp, surfPointsFlat} sizes (may
+ * be NULL).  Both handles on one device (EINVAL otherwise, before any device
+ * call). */
+int slio_lvx_process_cloud(slio_lvx_handle m, void* reg, const float* xyzi, int64_t n,
+                           float transform_aft_mapped[6], int32_t* iterations, int32_t counts[3]);
 /* transformTobeMapped / transformAftMapped / transformLastMapped; any may be NULL. */
 int slio_lvx_get_transforms(slio_lvx_handle m, float tobe_mapped[6], float aft_mapped[6],
                             float last_mapped[6]);

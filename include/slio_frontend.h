@@ -330,6 +330,75 @@ int slio_lego_odom_pass(slio_lego_handle h, int kind, int iter_count, const floa
 int slio_lego_odom_step(int kind, const float AtA[9], const float AtB[3], int32_t nsel, int iter_count,
                         float transform_cur[6], int* is_degenerate, float matP[9], int* keep_going);
 
+/* ======================================================================
+ * livox_mapping scanRegistration (src/livox_mapping/src/scanRegistration.cpp;
+ * every path:line below is in that file): laserCloudHandler :152-534 on the
+ * device.  One opaque handle owns the buffers of one device and one stream.
+ * Input: n x {x, y, z, intensity} float32 in the message's order.  A run is
+ *   prepare   :157-194  the first min(n, 32000) points, the finite ones in
+ *                       order, intensity = scanID + intensity / 10000
+ *   loop 1    :212-325  the strided pass (i += 4 where right_curvature < 0.01,
+ *                       else 1): flat points (1), surf-surf corners (150)
+ *   loop 2    :327-483  per point: outliers (250), break points (100), the
+ *                       break-point select (a point that fails goes to 0)
+ *   collect   :486-508  flag 1 -> surfPointsFlat, 100 / 150 ->
+ *                       cornerPointsSharp, in index order
+ * as a fixed number of launches (six, whatever n) and ONE host wait, the copy
+ * of the three counts.  The three clouds stay on the device
+ * (slio_lvx_feed_device, slio.h) until the next run.
+ *
+ * Stated departures from the reference:
+ *  - atan2 of two floats is the double function rounded to float (the
+ *    library's convention); where the device's double atan2 differs from the
+ *    host's in the last place AND the rounding to float does not hide it, the
+ *    scan id of a point within that distance of a multiple of 9 degrees may
+ *    differ.  The intensity is the only output it reaches;
+ *  - dis, dis2 and theta2 (:172-176, :488-493) are dead and not computed; the
+ *    scan id of a point that is dropped is not evaluated;
+ *  - Eigen's normalize() is 3.3's, which leaves a zero vector as it is.
+ * Errors as in slio.h; argument errors are reported before any device call.
+ * ====================================================================== */
+typedef struct slio_lreg* slio_lreg_handle;
+
+typedef struct slio_lreg_params {
+  int32_t device;
+  int32_t max_points; /* input capacity, 1 .. 32000 = CloudFeatureFlag's size (:53) */
+  int32_t reserved[6];
+} slio_lreg_params;
+
+/* device 0, max_points 32000 (:53, :158). */
+int slio_lreg_params_default(slio_lreg_params* p);
+/* EINVAL: max_points outside 1 .. 32000, no such device. */
+int slio_lreg_create(slio_lreg_handle* out, const slio_lreg_params* p);
+int slio_lreg_destroy(slio_lreg_handle h);
+/* laserCloudHandler (:152-534) on xyzi[n * 4].  Points past max_points are
+ * not read (:158).  counts = {laserCloud, cornerPointsSharp, surfPointsFlat}
+ * sizes.  EINVAL: n < 0, null cloud with n > 0, null counts. */
+int slio_lreg_run(slio_lreg_handle h, const float* xyzi, int64_t n, int32_t counts[3]);
+/* laserCloud (:189-190, :518) of the last run: counts[0] x 4.  ESTATE without
+ * a run; ECAPACITY when cap < counts[0]. */
+int slio_lreg_get_cloud(slio_lreg_handle h, float* xyzi, int64_t cap);
+/* kind 0: cornerPointsSharp (:505-507), kind 1: surfPointsFlat (:500-503). */
+int slio_lreg_get_features(slio_lreg_handle h, int kind, float* xyzi, int64_t cap);
+/* For tests: CloudFeatureFlag[0 .. counts[0]) after loop 2 and, per point, 1
+ * where loop 1 (:212) visited it.  Either may be NULL. */
+int slio_lreg_get_flags(slio_lreg_handle h, int32_t* flags, uint8_t* visited);
+/* The shape of the kernel that resolves loop 1's chain: thread t owns the
+ * loop positions [5 + t * per_thread, 5 + (t + 1) * per_thread), one workgroup
+ * owns per_workgroup of them (all 32000: there is no seam between workgroups). */
+int slio_lreg_chain_tile(int32_t* per_thread, int32_t* per_workgroup);
+/* -- host only, callable without a GPU -- */
+/* The whole handler as its literal serial loops.  Outputs sized for min(n,
+ * 32000) points; any of flags, visited, cloud, corner, surf, stats may be
+ * NULL.  stats[12] = visits with stride 1, with stride 4, flag[i-2] = 1
+ * writes (:242), flag[i+2] = 1 writes (:272), 150 set (:322), outliers (:358),
+ * break test entered left (:366) / right (:405), 100 set (:449), 100 kept
+ * (:475), 100 reset (:478), resets that erased a flag of loop 1. */
+int slio_lreg_classify_host(const float* xyzi, int64_t n, int32_t* flags, uint8_t* visited, float* cloud,
+                            float* corner, float* surf, int32_t counts[3], int32_t* stats);
+/* plane_judge (:64-120) on xyz[num * 3], 1 <= num <= 64. */
+int slio_lreg_plane_judge(const float* xyz, int32_t num, int32_t threshold, int32_t* is_plane);
+
 #ifdef __cplusplus
 }
 #endif

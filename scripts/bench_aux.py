@@ -26,6 +26,11 @@
             call and its split (select + gather, downsample, optimise, update),
             iterations, map and cube sizes, host waits, the last call once more
             through the host restatement (only when named)
+  livox_reg livox_mapping's scanRegistration (LivoxScanRegistration: slio_lreg_*) on a
+            dense continuous-curve frame of about 24,000 returns: ms per registration,
+            the counts, the host restatement beside it; then process_cloud (sensor's
+            cloud to pose) over a short drive: ms per call, of which the registration
+            (only when named)
 One JSON line per measurement (host wall clock around synchronous calls)."""
 import ctypes as C
 import json
@@ -632,8 +637,67 @@ def livox_map(calls=12, n_scan=20000):
     lock.close()
 
 
+def livox_reg(n_rays=31000, frames_n=8, reps=20):
+    """livox_mapping's scanRegistration (LivoxScanRegistration: slio_lreg_*) on
+    synth.make_scan_curve's dense frame (one continuous curve, about 24,000
+    returns): ms per registration (the upload, six launches and the wait for
+    the counts), the counts, the host restatement (slio_lreg_classify_host)
+    beside it; then `process_cloud` over a short drive, 0.25 m per frame: ms
+    per call, of which the registration, and the same frames through
+    laserCloudHandler + process (clouds down and up again)."""
+    from agi_lidar_slam_amd import synth
+    from agi_lidar_slam_amd.livox_map import LivoxMapping
+    from agi_lidar_slam_amd.livox_reg import LivoxScanRegistration, classify_host
+    seed = 20261015
+    scene = synth.make_scene(seed, 1000)
+    anchor = np.array([synth.SENSOR_STREET[0] - 3.0, synth.SENSOR_STREET[1] + 0.2, 1.6])
+    sc = synth.with_street_furniture(scene, anchor, 0.0)
+    frames = [synth.make_scan_curve(sc, anchor + [0.25 * k, 0.0, 0.0], 0.0, n_rays, k0=137 * k, seed=seed + k,
+                                    furniture=False) for k in range(frames_n)]
+    reg = LivoxScanRegistration()
+    reg.run(frames[0])                                   # warm-up
+    ms_reg, counts = t_ms(lambda: reg.run(frames[0]), reps)
+    ms_host, host = t_ms(lambda: classify_host(frames[0]), 3)
+    full, corner, surf = reg.laserCloudHandler(frames[0])
+    same = bool(np.array_equal(host["flags"], reg.flags()[0]) and np.array_equal(host["corner"], corner)
+                and np.array_equal(host["surf"], surf) and np.array_equal(host["cloud"], full))
+    dev, via_host = LivoxMapping(), LivoxMapping()
+    reg2 = LivoxScanRegistration()
+    rows = []
+    for fr in frames:
+        t0 = time.perf_counter()
+        dev.process_cloud(reg, fr)
+        t1 = time.perf_counter()
+        reg2.run(fr)
+        t2 = time.perf_counter()
+        _, c, s = reg2.laserCloudHandler(fr)
+        via_host.process(c[:, :3], s[:, :3])
+        t3 = time.perf_counter()
+        rows.append(dict(ms_process_cloud=(t1 - t0) * 1e3, ms_registration=(t2 - t1) * 1e3,
+                         ms_handler_plus_process=(t3 - t2) * 1e3, iterations=dev.iterations,
+                         counts=[int(v) for v in reg.counts],
+                         same_pose=bool(np.array_equal(dev.transformTobeMapped, via_host.transformTobeMapped))))
+    later = rows[1:]
+    mean = lambda key: float(np.mean([r[key] for r in later]))  # noqa: E731
+    print(json.dumps({
+        "bench": "livox_reg", "returns": int(len(frames[0])), "ms_per_registration": ms_reg,
+        "counts_cloud_corner_surf": [int(v) for v in counts], "ms_host_restatement": ms_host,
+        "host_same_bits_as_device": same, "frames": len(rows), "first_call": rows[0],
+        "mean_after_first": {key: mean(key) for key in ("ms_process_cloud", "ms_registration",
+                                                        "ms_handler_plus_process", "iterations")},
+        "estimated_distance_moved": float(np.linalg.norm(dev.transformTobeMapped[3:])),
+        "true_distance_moved": 0.25 * (len(rows) - 1),
+        "launches_per_registration": 6, "host_waits_per_registration": 1,
+        "host_waits_per_process_cloud": "those of process (2 maps + 2 feed + 1 per iteration + 2 update) + 1",
+        "kernel_times": "not measured"}), flush=True)
+    for h in (dev, via_host, reg, reg2):
+        h.close()
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "livox_reg" in what:
+        livox_reg()
     if "livox_map" in what:
         livox_map()
     if "lego_map" in what:
