@@ -281,6 +281,8 @@ SIGNATURES = {
     "slio_icp_params_default": (C.c_int, [C.POINTER(SlioIcpParams)]),
     "slio_icp_state_init": (C.c_int, [C.POINTER(SlioIcpState), _FP]),
     "slio_icp_step": (C.c_int, [_DP, C.c_int64, C.POINTER(SlioIcpParams), C.POINTER(SlioIcpState), _FP, _IP]),
+    "slio_icp_align": (C.c_int, [_P, C.POINTER(SlioIcpParams), _FP, C.c_double, C.c_int32,
+                                 C.POINTER(SlioIcpState), _DP, _I64P]),
     "slio_scan_upload_voxel": (C.c_int, [_P, _FP, _FP, _FP, C.c_int64, C.c_float, _I64P]),
     "slio_scan_download": (C.c_int, [_P, _FP, _FP, _FP]),
     "slio_map_add_points": (C.c_int, [_P, _FP, _FP, _FP, C.c_int64, C.c_int, C.c_float, _I64P]),
@@ -378,6 +380,10 @@ SIGNATURES = {
     "slio_lmap_save_keyframe": (C.c_int, [_P, _FP, _IP]),
     "slio_lmap_get_key_poses": (C.c_int, [_P, _FP, C.c_int32, _IP]),
     "slio_lmap_clear": (C.c_int, [_P]),
+    "slio_lmap_set_key_poses": (C.c_int, [_P, _FP, C.c_int32]),
+    "slio_lmap_loop_clouds": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _I64P]),
+    "slio_lmap_detect_loop": (C.c_int, [_FP, _DP, C.c_int32, _FP, C.c_double, C.c_float, C.c_double, _IP]),
+    "slio_lmap_loop_correction": (C.c_int, [_FP, _FP, _FP, C.c_double, _FP, _FP, _FP]),
     "slio_lmap_associate_to_map": (C.c_int, [_FP, _FP, _FP, _FP]),
     "slio_lmap_transform_update": (C.c_int, [_FP, _FP, C.c_double, C.c_float, _DP, _FP, _FP, C.c_int32, C.c_int32,
                                              _IP, _FP, _FP]),

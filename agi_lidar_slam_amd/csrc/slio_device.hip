@@ -7114,10 +7114,43 @@ int slio_iterate_async(slio_handle h, const slio_pose* x, int do_search, int ext
 // c's scan (slio_s2m_loop_cloud, as_scan).  The callers are in
 // slio_mapopt.hip; the VoxelGrid and the index build it drives stay here.
 int slio::kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float leaf, bool as_scan,
-                      int64_t counts[2], const char* who, int form) {
+                      int64_t counts[2], const char* who, int form, bool pass_through) {
   hipStream_t st = c.stream;
   int rc = nbr_settle_shared(c);  // the map (scan) it was searched on (with) is replaced
   if (rc) return rc;
+  if (as_scan && pass_through) {
+    // the concatenation itself becomes the scan (no VoxelGrid; non-finite
+    // points stay): the gather writes the scan buffers, the end state is
+    // slio_scan_upload's
+    if (n > c.prm.max_points) {
+      set_error(std::string(who) + ": the concatenation exceeds max_points");
+      return SLIO_ECAPACITY;
+    }
+    if ((rc = ensure_scan_buffers(c))) return rc;
+    if (n > 0) {
+      if (const hipError_t e = MapDev::take(c.kfb[1], sizeof(KfSeg) * seg.size())) {
+        set_error(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+        return SLIO_ENOMEM;
+      }
+      KfSeg* dseg = (KfSeg*)c.kfb[1].p;
+      VgWork w{};  // (only for the box the gather folds)
+      if ((rc = vg_begin(c, n, who, w))) return rc;
+      SLIO_HIP(hipMemcpyAsync(dseg, seg.data(), sizeof(KfSeg) * seg.size(), hipMemcpyHostToDevice, st));
+      const int nblk = (int)std::min<int64_t>((n + kKfTile - 1) / kKfTile, 1024);
+      if (form == 0)
+        k_kf_gather<0><<<nblk, kKfTile, 0, st>>>(dseg, (int)seg.size(), n, c.bx, c.by, c.bz, w.bb);
+      else
+        k_kf_gather<1><<<nblk, kKfTile, 0, st>>>(dseg, (int)seg.size(), n, c.bx, c.by, c.bz, w.bb);
+      SLIO_HIP(hipGetLastError());
+      SLIO_HIP(hipMemsetAsync(c.sel, 0, n, st));
+      // the call's one host wait: `seg` has left the host, the stores' arenas have been read
+      SLIO_HIP(hipStreamSynchronize(st));
+    }
+    c.n = n;
+    c.searched = false;
+    if (counts) counts[0] = counts[1] = n;
+    return SLIO_OK;
+  }
   if (as_scan) {
     float *cx = nullptr, *cy = nullptr, *cz = nullptr;
     if (n > 0) {

@@ -218,8 +218,9 @@ struct Ctx {
   hipEvent_t kf_ev = nullptr; // orders another handle's assembly after this store's pushes
                               // (slio_s2m_loop_cloud)
   // loop-closure ICP (slio_icp_correspond): the working cloud (SoA), the last
-  // pass's map id and squared distance per working point, the workgroup partials
-  MapDev::Buf icp[4];
+  // pass's map id and squared distance per working point, the workgroup
+  // partials, the device-resident loop's state (slio_icp_align)
+  MapDev::Buf icp[5];
   int64_t icp_n = -1;         // working points (-1: no pass yet)
   int64_t icp_far = 0;        // queries the last pass sent down the far path
   IkfCtl* ctl = nullptr;   // device-resident update state (HBM)
@@ -324,10 +325,12 @@ int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float* dz_, i
                  int64_t* n_down);
 // Gather-transform the n points of `seg` (FORM `form` of k_kf_gather) into one
 // concatenation on c's stream, VoxelGrid it with edge `leaf`, and make the
-// result c's map or, as_scan, c's scan.  The one map-building entry of the
-// back-ends: the VoxelGrid and the index build stay in slio_device.hip.
+// result c's map or, as_scan, c's scan.  pass_through (with as_scan only): no
+// VoxelGrid, the concatenation itself becomes the scan, `leaf` is not read.
+// The one map-building entry of the back-ends: the VoxelGrid and the index
+// build stay in slio_device.hip.
 int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float leaf, bool as_scan, int64_t counts[2],
-                const char* who, int form = 0);
+                const char* who, int form = 0, bool pass_through = false);
 #pragma GCC visibility pop
 
 }  // namespace slio

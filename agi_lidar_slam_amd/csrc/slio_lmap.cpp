@@ -114,6 +114,25 @@ void associate_to_map(const float ts[6], const float tb[6], const float ta[6], f
   tm[5] = ta[5] - (-fsin(tm[1]) * x2 + fcos(tm[1]) * z2);
 }
 
+// pcl::getTransformation (pcl/common/impl/eigen.hpp) in float: rows 0..2 of the affine
+void get_transformation(float x, float y, float z, float roll, float pitch, float yaw, float t[12]) {
+  const float A = fcos(yaw), B = fsin(yaw), C = fcos(pitch), D = fsin(pitch), E = fcos(roll), F = fsin(roll),
+              DE = D * E, DF = D * F;
+  t[0] = A * C, t[1] = A * DF - B * E, t[2] = B * F + A * DE, t[3] = x;
+  t[4] = B * C, t[5] = A * E + B * DF, t[6] = B * DE - A * F, t[7] = y;
+  t[8] = -D, t[9] = C * F, t[10] = C * E, t[11] = z;
+}
+
+// pcl::getTranslationAndEulerAngles
+void translation_and_euler(const float t[12], float& x, float& y, float& z, float& roll, float& pitch, float& yaw) {
+  x = t[3];
+  y = t[7];
+  z = t[11];
+  roll = fatan2(t[9], t[10]);
+  pitch = fasin(-t[8]);
+  yaw = fatan2(t[4], t[0]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -200,6 +219,64 @@ int slio_lmap_keyframe_decision(const float prev_pos[3], const float cur_pos[3],
   bool save_this = true;
   if ((double)d < distance) save_this = false;
   *save = (save_this || nkeys == 0) ? 1 : 0;
+  return SLIO_OK;
+}
+
+int slio_lmap_detect_loop(const float* key_xyz, const double* key_time, int32_t nkeys, const float cur_pos[3],
+                          double t, float radius, double time_diff, int32_t* closest) {
+  if (!closest || !cur_pos || nkeys < 0 || (nkeys > 0 && (!key_xyz || !key_time)) || !(radius >= 0.0f) ||
+      !(time_diff >= 0.0)) {
+    set_error("slio_lmap_detect_loop: bad arguments");
+    return SLIO_EINVAL;
+  }
+  // :871-883: the radius search's results in ascending squared distance (equal
+  // distances: the lower key); the first one far enough in time wins.  Picking
+  // the smallest (distance, key) among the keys that pass both tests is the
+  // same key.
+  *closest = -1;
+  const float r2 = radius * radius;
+  float best = 0.0f;
+  for (int32_t k = 0; k < nkeys; ++k) {
+    const float dx = key_xyz[3 * k] - cur_pos[0], dy = key_xyz[3 * k + 1] - cur_pos[1],
+                dz = key_xyz[3 * k + 2] - cur_pos[2];
+    const float d = (dx * dx + dy * dy) + dz * dz;
+    if (!(d < r2)) continue;
+    if (!(std::fabs(key_time[k] - t) > time_diff)) continue;
+    if (*closest < 0 || d < best) {
+      *closest = k;
+      best = d;
+    }
+  }
+  return SLIO_OK;
+}
+
+int slio_lmap_loop_correction(const float final_T[16], const float latest_pose6[6], const float closest_pose6[6],
+                              double fitness, float pose_from[6], float pose_to[6], float* noise) {
+  if (!final_T || !latest_pose6 || !closest_pose6 || !pose_from || !pose_to || !noise) {
+    set_error("slio_lmap_loop_correction: null argument");
+    return SLIO_EINVAL;
+  }
+  float x, y, z, roll, pitch, yaw;
+  translation_and_euler(final_T, x, y, z, roll, pitch, yaw);  // :994-997 (rows 0..2 of the 4x4)
+  float corr[12], wrong[12], ok[12];
+  get_transformation(z, x, y, yaw, roll, pitch, corr);  // correctionLidarFrame (:998-999)
+  const float* p = latest_pose6;                        // {rx, ry, rz, tx, ty, tz} = {roll, pitch, yaw, x, y, z}
+  get_transformation(p[5], p[3], p[4], p[2], p[0], p[1], wrong);  // tWrong (:1032-1036)
+  // tCorrect = correctionLidarFrame * tWrong (:1002), an affine product:
+  // linear = L1 L2, translation = L1 t2 + t1, every sum in index order
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c)
+      ok[4 * r + c] = (corr[4 * r] * wrong[c] + corr[4 * r + 1] * wrong[4 + c]) + corr[4 * r + 2] * wrong[8 + c];
+    ok[4 * r + 3] =
+        ((corr[4 * r] * wrong[3] + corr[4 * r + 1] * wrong[7]) + corr[4 * r + 2] * wrong[11]) + corr[4 * r + 3];
+  }
+  translation_and_euler(ok, x, y, z, roll, pitch, yaw);  // :1003
+  const float from[6] = {x, y, z, roll, pitch, yaw};
+  const float* q = closest_pose6;
+  const float to[6] = {q[5], q[3], q[4], q[2], q[0], q[1]};  // pclPointTogtsamPose3 (:1025-1030)
+  std::memcpy(pose_from, from, sizeof(from));
+  std::memcpy(pose_to, to, sizeof(to));
+  *noise = (float)fitness;  // float noiseScore = icp.getFitnessScore() (:1009)
   return SLIO_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -21,6 +22,7 @@
 #include "slio_cvsolve.hpp"
 #include "slio_device.hpp"
 #include "slio_frontend.h"
+#include "slio_icp.hpp"
 #include "slio_livox.hpp"
 #include "slio_plane.hpp"
 
@@ -763,10 +765,10 @@ int slio_s2m_normal_equations(slio_handle h_corner, slio_handle h_surf, const fl
 // reduces its rows (block_sums_256), one partial per workgroup.
 constexpr int kIcpSums = 18;  // p (3), q (3), q p^T (9), sqd, correspondences, far queries
 // (sx / sy / sz may be wx / wy / wz: no __restrict__ on the six)
-__global__ __launch_bounds__(256) void k_icp_pass(const MapView map, const float* sx, const float* sy,
-                                                  const float* sz, int64_t n, Aff12 T, double max_sq, float* wx,
-                                                  float* wy, float* wz, int32_t* __restrict__ idx,
-                                                  float* __restrict__ sqd, double* __restrict__ partial) {
+__device__ __forceinline__ void icp_pass_body(const MapView& map, const float* sx, const float* sy, const float* sz,
+                                              int64_t n, const Aff12& T, double max_sq, float* wx, float* wy,
+                                              float* wz, int32_t* __restrict__ idx, float* __restrict__ sqd,
+                                              double* __restrict__ partial) {
   __shared__ int far_cnt;
   __shared__ float4 far_q[256];
   __shared__ uint8_t far_slot[256];
@@ -864,7 +866,179 @@ __global__ __launch_bounds__(256) void k_icp_pass(const MapView map, const float
   block_sums_256(v, partial);
 }
 
+// the lockstep path's pass (slio_icp_correspond): the transform is a kernel argument
+__global__ __launch_bounds__(256) void k_icp_pass(const MapView map, const float* sx, const float* sy,
+                                                  const float* sz, int64_t n, Aff12 T, double max_sq, float* wx,
+                                                  float* wy, float* wz, int32_t* __restrict__ idx,
+                                                  float* __restrict__ sqd, double* __restrict__ partial) {
+  icp_pass_body(map, sx, sy, sz, n, T, max_sq, wx, wy, wz, idx, sqd, partial);
+}
+
+// ---------------------------------------------------------------- the device-resident ICP loop
+// slio_icp_align: icp.align and getFitnessScore without a host wait per
+// iteration.  The loop's state lives in one small struct in HBM; an iteration
+// is two launches on the handle's stream, the wide pass (k_icp_pass_dev: the
+// lockstep pass's body, its transform read from the struct) and a
+// one-workgroup tail (k_icp_tail: the workgroups' partials added in ascending
+// workgroup order, one lane per entry, then slio::icp::step on one thread).
+// Stream order is the only synchronisation: no kernel waits for another
+// workgroup, and a launch that finds `done` set returns at once, so the host
+// may enqueue a batch of iterations past the end of the loop.
+struct IcpDev {
+  slio_icp_state st;
+  slio_icp_params prm;
+  float delta[16];       // the next pass's transform (the guess before the first pass)
+  int32_t done;
+  int32_t fit_done;      // the fitness pass's tail has run
+  int64_t ncorr;         // correspondences of the last loop pass
+  int64_t far_first;     // far queries of the first pass
+  double fit[kIcpSums];  // the fitness pass: sums, correspondences, far queries
+};
+
+// fit == 0: a loop pass, T = delta, nothing happens once `done` is set;
+// fit == 1: the fitness pass, T = final_T
+__global__ __launch_bounds__(256) void k_icp_pass_dev(const IcpDev* __restrict__ dev, int fit, const MapView map,
+                                                      const float* sx, const float* sy, const float* sz, int64_t n,
+                                                      double max_sq, float* wx, float* wy, float* wz,
+                                                      int32_t* __restrict__ idx, float* __restrict__ sqd,
+                                                      double* __restrict__ partial) {
+  if (!fit && dev->done) return;  // (uniform over the launch, before any barrier)
+  Aff12 T;
+  const float* m = fit ? dev->st.final_T : dev->delta;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) T.m[k] = m[k];
+  icp_pass_body(map, sx, sy, sz, n, T, max_sq, wx, wy, wz, idx, sqd, partial);
+}
+
+// <<<1, 64>>>.  The sums as slio_icp_correspond forms them on the host:
+// acc[k] = 0, then acc[k] = acc[k] + partial[b][k] for b = 0 .. nb - 1.
+__global__ __launch_bounds__(64) void k_icp_tail(IcpDev* __restrict__ dev, int fit, int first,
+                                                 const double* __restrict__ partial, int nb) {
+  if (!fit && dev->done) return;  // (uniform, before the barrier)
+  __shared__ double acc_s[kIcpSums];
+  const int k = threadIdx.x;
+  if (k < kIcpSums) {
+    double acc = 0.0;
+    for (int b = 0; b < nb; ++b) acc = acc + partial[(int64_t)b * kIcpSums + k];
+    acc_s[k] = acc;
+    if (fit) dev->fit[k] = acc;
+  }
+  __syncthreads();
+  if (k != 0) return;
+  if (fit) {
+    dev->fit_done = 1;
+    return;
+  }
+  double sums[16];
+  for (int a = 0; a < 16; ++a) sums[a] = acc_s[a];
+  const int64_t ncorr = (int64_t)llround(acc_s[16]);
+  dev->ncorr = ncorr;
+  if (first) dev->far_first = (int64_t)llround(acc_s[17]);
+  slio_icp_state st = dev->st;
+  const slio_icp_params prm = dev->prm;
+  float delta[16];
+  int done = 0;
+  slio::icp::step(sums, ncorr, &prm, &st, delta, &done);
+  dev->st = st;
+  for (int a = 0; a < 16; ++a) dev->delta[a] = delta[a];
+  dev->done = done;
+}
+
+constexpr int kIcpBatchDefault = 8;  // iterations enqueued between two reads of the state
+
 extern "C" {
+
+int slio_icp_align(slio_handle h, const slio_icp_params* prm, const float guess[16], double max_dist, int32_t batch,
+                   slio_icp_state* out, double* fitness, int64_t* far_first) {
+  if (!h) {
+    set_error("null handle");
+    return SLIO_EINVAL;
+  }
+  if (!prm || !out || !(max_dist >= 0.0) || h->c.prm.nranks != 1) {
+    set_error("slio_icp_align: bad arguments");
+    return SLIO_EINVAL;
+  }
+  Ctx& c = h->c;
+  if (!c.map || (!c.bx && c.n > 0)) {
+    set_error("slio_icp_align: map and scan needed");
+    return SLIO_ESTATE;
+  }
+  if (batch <= 0) batch = kIcpBatchDefault;
+  IcpDev hd;
+  std::memset(&hd, 0, sizeof(hd));
+  slio_icp_state_init(&hd.st, guess);
+  hd.prm = *prm;
+  std::memcpy(hd.delta, hd.st.final_T, sizeof(hd.delta));
+  const int64_t n = c.n;
+  c.icp_far = 0;
+  c.icp_n = n;
+  if (fitness) *fitness = DBL_MAX;  // getFitnessScore without a correspondence
+  if (far_first) *far_first = 0;
+  if (n == 0) {
+    // the lockstep loop's first step on zero sums: NO_CORRESPONDENCES
+    hd.st.convergence_state = SLIO_ICP_NO_CORRESPONDENCES;
+    *out = hd.st;
+    return SLIO_OK;
+  }
+  SLIO_HIP(hipSetDevice(c.prm.device));
+  const int nb = (int)((n + 255) / 256);
+  hipError_t e;
+  if ((e = MapDev::take(c.icp[0], 12 * n)) || (e = MapDev::take(c.icp[1], 4 * n)) ||
+      (e = MapDev::take(c.icp[2], 4 * n)) || (e = MapDev::take(c.icp[3], 8 * (size_t)kIcpSums * nb)) ||
+      (e = MapDev::take(c.icp[4], sizeof(IcpDev)))) {
+    c.icp_n = -1;
+    set_error(std::string("slio_icp_align: hipMalloc: ") + hipGetErrorString(e));
+    return SLIO_ENOMEM;
+  }
+  float* wx = (float*)c.icp[0].p;
+  float* wy = wx + n;
+  float* wz = wx + 2 * n;
+  int32_t* idx = (int32_t*)c.icp[1].p;
+  float* sqd = (float*)c.icp[2].p;
+  double* part = (double*)c.icp[3].p;
+  IcpDev* dev = (IcpDev*)c.icp[4].p;
+  if (int rc = map_refresh(c); rc) return rc;
+  std::shared_lock<std::shared_mutex> lk(c.map->mu);
+  if (int rc = map_read_sync(c)) return rc;
+  const CoarseView cv{c.map->cg, c.map->clo, c.map->chi};
+  const MapView mv{c.map->g,      c.map->n,    c.map->pts,    c.map->start, c.map->blk,
+                   c.map->bstart, c.map->nblk, c.map->ncells, cv};
+  // (pageable source: the copy has left `hd` when the call returns)
+  SLIO_HIP(hipMemcpyAsync(dev, &hd, sizeof(hd), hipMemcpyHostToDevice, c.stream));
+  const double max_sq = max_dist * max_dist;
+  // every turn of the loop ends it or counts one iteration, so max_iterations
+  // turns (one, where that is not positive) always set `done`
+  const int64_t most = std::max<int64_t>(prm->max_iterations, 1);
+  const Rb rb{&hd, dev, sizeof(hd)};
+  int64_t turns = 0;
+  while (!hd.done) {
+    if (turns >= most) {
+      c.icp_n = -1;
+      set_error("slio_icp_align: the device loop did not end");
+      return SLIO_EDEVICE;
+    }
+    for (int32_t b = 0; b < batch && turns < most; ++b, ++turns) {
+      const bool first = turns == 0;
+      k_icp_pass_dev<<<nb, 256, 0, c.stream>>>(dev, 0, mv, first ? c.bx : wx, first ? c.by : wy, first ? c.bz : wz,
+                                               n, max_sq, wx, wy, wz, idx, sqd, part);
+      k_icp_tail<<<1, 64, 0, c.stream>>>(dev, 0, first ? 1 : 0, part, nb);
+    }
+    SLIO_HIP(hipGetLastError());
+    SLIO_HIP(readback(c.stream, &rb, 1));
+  }
+  // getFitnessScore: the source at final_T, no gate
+  k_icp_pass_dev<<<nb, 256, 0, c.stream>>>(dev, 1, mv, c.bx, c.by, c.bz, n, (double)INFINITY, wx, wy, wz, idx, sqd,
+                                           part);
+  k_icp_tail<<<1, 64, 0, c.stream>>>(dev, 1, 0, part, nb);
+  SLIO_HIP(hipGetLastError());
+  SLIO_HIP(readback(c.stream, &rb, 1));
+  *out = hd.st;
+  const int64_t nfit = (int64_t)llround(hd.fit[16]);
+  c.icp_far = (int64_t)llround(hd.fit[17]);
+  if (fitness && nfit > 0) *fitness = hd.fit[15] / (double)nfit;
+  if (far_first) *far_first = hd.far_first;
+  return SLIO_OK;
+}
 
 int slio_icp_correspond(slio_handle h, const float T[16], int from_scan, double max_dist, double sums[16],
                         int64_t* ncorr) {
@@ -1233,7 +1407,9 @@ int slio_s2m_loop_cloud(slio_handle h_dst, slio_handle h_corner, slio_handle h_s
 // transformFusion, the keyframe decision) are in slio_lmap.cpp.
 struct slio_lmap {
   slio_lmap_params prm{};
-  slio_handle h[4] = {nullptr, nullptr, nullptr, nullptr};
+  // (h[SLIO_LMAP_LOOP] is created on first use: a mapper without loop closure
+  // allocates what it always did)
+  slio_handle h[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   std::vector<float> poses6;   // cloudKeyPoses6D: {rx, ry, rz, tx, ty, tz} per key
   bool coeff_ok[2] = {false, false};
 };
@@ -1343,6 +1519,30 @@ static int lmap_coeff_state(slio_lmap* m, int kind, const char* who) {
   return SLIO_OK;
 }
 
+// the loop closure's handle (map = nearHistorySurfKeyFrameCloudDS, scan =
+// latestSurfKeyFrameCloud), on the mapper's stream
+static int lmap_loop_handle(slio_lmap* m) {
+  if (m->h[SLIO_LMAP_LOOP]) return SLIO_OK;
+  slio_params sp;
+  slio_params_default(&sp);
+  sp.device = m->prm.device;
+  sp.max_points = m->prm.max_points;
+  sp.grid_cell = m->prm.grid_cell;
+  slio_handle h = nullptr;
+  int rc = slio_create(&h, &sp);
+  if (!rc) rc = slio_set_stream(h, (void*)m->h[0]->c.stream);
+  if (!rc) rc = ensure_scan_buffers(h->c);
+  if (rc) {
+    if (h) {
+      (void)slio_set_stream(h, nullptr);
+      (void)slio_destroy(h);
+    }
+    return rc;
+  }
+  m->h[SLIO_LMAP_LOOP] = h;
+  return SLIO_OK;
+}
+
 extern "C" {
 
 int slio_lmap_params_default(slio_lmap_params* p) {
@@ -1370,7 +1570,7 @@ int slio_lmap_destroy(slio_lmap_handle m) {
   if (!m) return SLIO_OK;
   int rc = SLIO_OK;
   // (handle 0 owns the stream the others borrow: destroyed last)
-  for (int i = 3; i >= 0; --i)
+  for (int i = 4; i >= 0; --i)
     if (m->h[i]) {
       if (i > 0) (void)slio_set_stream(m->h[i], nullptr);
       const int r = slio_destroy(m->h[i]);
@@ -1413,10 +1613,12 @@ int slio_lmap_create(slio_lmap_handle* out, const slio_lmap_params* p) {
 
 int slio_lmap_get_handle(slio_lmap_handle m, int which, slio_handle* out) {
   if (int rc = lmap_check(m, "slio_lmap_get_handle")) return rc;
-  if (which < 0 || which > 3 || !out) {
+  if (which < 0 || which > SLIO_LMAP_LOOP || !out) {
     set_error("slio_lmap_get_handle: bad arguments");
     return SLIO_EINVAL;
   }
+  if (which == SLIO_LMAP_LOOP)
+    if (int rc = lmap_loop_handle(m)) return rc;
   // the caller may upload a scan or a map through it: nothing cached here survives that
   m->coeff_ok[0] = m->coeff_ok[1] = false;
   *out = m->h[which];
@@ -1605,6 +1807,48 @@ int slio_lmap_get_key_poses(slio_lmap_handle m, float* poses6, int32_t cap, int3
     }
     if (nk) std::memcpy(poses6, m->poses6.data(), sizeof(float) * m->poses6.size());
   }
+  return SLIO_OK;
+}
+
+int slio_lmap_set_key_poses(slio_lmap_handle m, const float* poses6, int32_t nkeys) {
+  if (int rc = lmap_check(m, "slio_lmap_set_key_poses")) return rc;
+  if (nkeys < 0 || (nkeys > 0 && !poses6) || (size_t)nkeys * 6 != m->poses6.size()) {
+    set_error("slio_lmap_set_key_poses: nkeys must equal the key-pose table's length (" +
+              std::to_string(m->poses6.size() / 6) + ")");
+    return SLIO_EINVAL;
+  }
+  if (nkeys) std::memcpy(m->poses6.data(), poses6, sizeof(float) * m->poses6.size());
+  return SLIO_OK;
+}
+
+int slio_lmap_loop_clouds(slio_lmap_handle m, int32_t latest, int32_t closest, int32_t search_num, float leaf,
+                          int64_t counts[4]) {
+  static const char* who = "slio_lmap_loop_clouds";
+  if (int rc = lmap_check(m, who)) return rc;
+  const int32_t nkeys = (int32_t)(m->poses6.size() / 6);
+  if (latest < 0 || latest >= nkeys || closest < 0 || closest >= nkeys || search_num < 0 || !(leaf > 0.0f)) {
+    set_error("slio_lmap_loop_clouds: key out of range, negative search_num or bad leaf");
+    return SLIO_EINVAL;
+  }
+  // :914-918: closest - search_num .. closest + search_num, skipping k < 0 and k > latest
+  std::vector<int32_t> tkeys;
+  for (int64_t k = (int64_t)closest - search_num; k <= (int64_t)closest + search_num; ++k)
+    if (k >= 0 && k <= latest) tkeys.push_back((int32_t)k);
+  std::vector<float> tposes(tkeys.size() * 6);
+  for (size_t i = 0; i < tkeys.size(); ++i) std::memcpy(&tposes[6 * i], &m->poses6[6 * (size_t)tkeys[i]], 24);
+  const Ctx* src[2] = {&m->h[SLIO_LMAP_CORNER]->c, &m->h[SLIO_LMAP_SURF]->c};
+  std::vector<KfSeg> sseg, tseg;
+  int64_t ns = 0, nt = 0;
+  if (int rc = kf_segments(src, 2, &latest, &m->poses6[6 * (size_t)latest], 1, sseg, ns, who, 1)) return rc;
+  if (int rc = kf_segments(src, 2, tkeys.data(), tposes.data(), (int32_t)tkeys.size(), tseg, nt, who, 1)) return rc;
+  if (int rc = lmap_loop_handle(m)) return rc;
+  SLIO_HIP(hipSetDevice(m->prm.device));
+  Ctx& cl = m->h[SLIO_LMAP_LOOP]->c;
+  int64_t k[4] = {0, 0, 0, 0};
+  if (int rc = kf_assemble(cl, sseg, ns, leaf, true, k, who, 1, true)) return rc;
+  if (int rc = kf_assemble(cl, tseg, nt, leaf, false, k + 2, who, 1)) return rc;
+  if (counts)
+    for (int i = 0; i < 4; ++i) counts[i] = k[i];
   return SLIO_OK;
 }
 

@@ -21,7 +21,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .lego_map import LegoMapping, TransformFusion, extract_surrounding  # noqa: F401  (the mapping back-end)
+from .lego_map import (LegoLoopClosure, LegoMapping, TransformFusion,  # noqa: F401  (the mapping back-end)
+                       extract_surrounding)
 
 IMU_QUE_LEN = 200  # imuQueLength (utility.h:42)
 

@@ -1,6 +1,9 @@
-"""LeGO-LOAM's mapping back-end (mapOptmization.cpp with loopClosureEnableFlag
-= false, transformFusion.cpp) on the device: the slio_lmap_* entries of
-include/slio.h behind the reference's member names.
+"""LeGO-LOAM's mapping back-end (mapOptmization.cpp, transformFusion.cpp) on
+the device: the slio_lmap_* entries of include/slio.h behind the reference's
+member names.  ``LegoMapping(loop_closure=True)`` is the reference with
+loopClosureEnableFlag = true: the recent-keyframe local map, performLoopClosure
+and correctPoses; the factor graph (GTSAM) stays with the caller, behind the
+``graph`` object.
 
 Everything is in LeGO-LOAM's camera-like frame; poses are float32
 ``{rx, ry, rz, tx, ty, tz}``.  The stated departures (tie rule of the 5-NN,
@@ -10,13 +13,56 @@ the uncached keyframe transforms) are listed in slio.h and DESIGN.md §3.13.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 from . import _lib as L
+from .lio_sam import icp_align_device, icp_align_lockstep
 
-CORNER, SURF_TOTAL, SURF, OUTLIER = 0, 1, 2, 3
+CORNER, SURF_TOTAL, SURF, OUTLIER, LOOP = 0, 1, 2, 3, 4
 IMU_QUE_LENGTH = 200   # imuQueLength (utility.h)
+SURROUNDING_KEYFRAME_SEARCH_NUM = 50     # surroundingKeyframeSearchNum (utility.h:92)
+HISTORY_KEYFRAME_SEARCH_RADIUS = 5.0     # historyKeyframeSearchRadius (utility.h:94)
+HISTORY_KEYFRAME_SEARCH_NUM = 25         # historyKeyframeSearchNum (utility.h:95)
+HISTORY_KEYFRAME_FITNESS_SCORE = 0.3     # historyKeyframeFitnessScore (utility.h:96)
+# performLoopClosure's ICP path when the caller names none.  The device loop:
+# on the 16 x 1800 sequence's sizes it measured faster than the lockstep loop
+# by more than the spread between runs
+LOOP_ICP_LOCKSTEP_DEFAULT = False
+
+
+class LegoLoopClosure(NamedTuple):
+    """A closure performLoopClosure found: the factor's keys (latest,
+    closest), its poses as GTSAM takes them ({x, y, z, roll, pitch, yaw} of
+    tCorrect; the closest key as {tz, tx, ty, rz, rx, ry}), the noise score,
+    and the ICP's iteration count and convergence state."""
+    latest: int
+    closest: int
+    pose_from: np.ndarray
+    pose_to: np.ndarray
+    noise: float
+    iterations: int
+    state: int
+
+
+def recent_keyframes(recent: list, latest_frame_id: int, nkeys: int,
+                     search_num: int = SURROUNDING_KEYFRAME_SEARCH_NUM):
+    """The recent-keyframe list of extractSurroundingKeyFrames (:1044-1089) as
+    key numbers: (list, latestFrameID) after the call.  While the list holds
+    fewer than search_num entries it is refilled whole, from the newest key
+    back, each pushed to the front (so ascending), and latestFrameID stays as
+    it is; once it holds search_num, a call with latestFrameID != nkeys - 1
+    pops the oldest entry and appends the latest key -- also when that key
+    already is the last entry, as on the first call after the list filled up."""
+    recent = list(recent)
+    if len(recent) < search_num:
+        recent = list(range(max(nkeys - search_num, 0), nkeys))
+    elif latest_frame_id != nkeys - 1:
+        recent.pop(0)
+        latest_frame_id = nkeys - 1
+        recent.append(latest_frame_id)
+    return recent, latest_frame_id
 
 
 def _pose_voxel_grid4(pts: np.ndarray, leaf: float) -> np.ndarray:
@@ -108,8 +154,16 @@ class LegoMapping:
     """mapOptmization's members and run() (:1807-1845) without loop closure,
     GTSAM, ROS or publishing."""
 
-    def __init__(self, device: int = 0, max_points: int = 100000, grid_cell: float = 0.0, **kw):
+    def __init__(self, device: int = 0, max_points: int = 100000, grid_cell: float = 0.0,
+                 loop_closure: bool = False, **kw):
         self.lib = L.load()
+        self.loop_closure = bool(loop_closure)     # loopClosureEnableFlag (utility.h:68)
+        self.keyTimes: list[float] = []            # cloudKeyPoses6D.time
+        self.recentKeyFrames: list[int] = []       # recent*CloudKeyFrames, as key numbers
+        self.latestFrameID = 0
+        self.aLoopIsClosed = False
+        self._corrected = None                     # the table graph.add_loop returned
+        self.graph = None
         p = L.SlioLmapParams()
         L.check(self.lib.slio_lmap_params_default(C.byref(p)), "lmap_params_default")
         p.device, p.max_points, p.grid_cell = device, max_points, grid_cell
@@ -142,6 +196,8 @@ class LegoMapping:
         self.trace: list[np.ndarray] = []          # lockstep: transformTobeMapped after every iteration
         self.saved_last = False
         self.tobe_associated = np.zeros(6, f)
+        self._last = np.zeros(6, f)                # transformLast
+        self.loop_counts = np.zeros(4, np.int64)
 
     def close(self):
         if self.m:
@@ -235,11 +291,17 @@ class LegoMapping:
     def extractSurroundingKeyFrames(self) -> np.ndarray:
         """:1098-1194.  Without key poses the reference returns at once and
         the maps stay empty (clearCloud): an empty key list here."""
-        if self.cloudKeyPoses3D.shape[0]:
-            self.surroundingExistingKeyPosesID, _ = extract_surrounding(
-                self.cloudKeyPoses3D, self.currentRobotPosPoint, self.surroundingExistingKeyPosesID,
-                self.params.search_radius, self.params.pose_leaf)
-        keys = np.array(self.surroundingExistingKeyPosesID, np.int32)
+        nkeys = self.cloudKeyPoses3D.shape[0]
+        if nkeys and self.loop_closure:      # :1042-1097
+            self.recentKeyFrames, self.latestFrameID = recent_keyframes(self.recentKeyFrames, self.latestFrameID,
+                                                                        nkeys)
+            keys = np.array(self.recentKeyFrames, np.int32)
+        else:
+            if nkeys:
+                self.surroundingExistingKeyPosesID, _ = extract_surrounding(
+                    self.cloudKeyPoses3D, self.currentRobotPosPoint, self.surroundingExistingKeyPosesID,
+                    self.params.search_radius, self.params.pose_leaf)
+            keys = np.array(self.surroundingExistingKeyPosesID, np.int32)
         L.check(self.lib.slio_lmap_extract(self.m, L.iptr(keys), keys.size, L.i64ptr(self.map_counts)),
                 "lmap_extract")
         return self.map_counts.copy()
@@ -317,7 +379,12 @@ class LegoMapping:
             self.transformUpdate()
 
     def saveKeyFramesAndFactor(self) -> bool:
-        """:1628-1767 with the key pose = transformTobeMapped (no GTSAM)."""
+        """:1628-1767.  The key pose is transformTobeMapped, or what
+        graph.add_keyframe(key, pose_from6, pose_to6) returns: pose_from6 =
+        transformLast and pose_to6 = transformAftMapped, both {rx, ry, rz, tx,
+        ty, tz} (the reference hands GTSAM their {rz, rx, ry, tz, tx, ty},
+        :1656-1693); for key 0 pose_from6 is None and pose_to6 is
+        transformTobeMapped (the prior factor)."""
         self.currentRobotPosPoint = self._aft[3:6].copy()
         save = C.c_int()
         nkeys = self.cloudKeyPoses3D.shape[0]
@@ -329,11 +396,19 @@ class LegoMapping:
             return False
         self.previousRobotPosPoint = self.currentRobotPosPoint.copy()
         pose = self._tobe.copy()
+        if self.graph is not None:
+            est = self.graph.add_keyframe(nkeys, self._last.copy() if nkeys else None,
+                                          self._aft.copy() if nkeys else self._tobe.copy())
+            pose = np.array(est, np.float32).reshape(6)
+        self._last = pose.copy() if nkeys else self._tobe.copy()    # transformLast (:1695-1696, :1745-1748)
+        self.keyTimes.append(float(self.timeLaserOdometry))         # thisPose6D.time (:1734)
         p3 = np.array([pose[3], pose[4], pose[5], nkeys], np.float32)
         self.cloudKeyPoses3D = np.vstack([self.cloudKeyPoses3D, p3[None]])
         self._poses6 = np.vstack([self._poses6, pose[None]])
         if nkeys + 1 > 1:   # :1737-1749
             self._aft = pose.copy()
+            if self.graph is not None:
+                self._tobe = pose.copy()
         key = C.c_int32()
         L.check(self.lib.slio_lmap_save_keyframe(self.m, L.fptr(pose), C.byref(key)), "lmap_save_keyframe")
         assert key.value == nkeys
@@ -356,4 +431,93 @@ class LegoMapping:
         self.downsampleCurrentScan(front_end)
         self.scan2MapOptimization(lockstep=lockstep)
         self.saveKeyFramesAndFactor()
+        self.correctPoses()
         return True
+
+    # ------------------------------------------------------------ loop closure
+    def set_key_poses(self, poses6) -> None:
+        """slio_lmap_set_key_poses: the whole key-pose table ({rx, ry, rz, tx,
+        ty, tz} per key); cloudKeyPoses3D / 6D follow."""
+        t = np.ascontiguousarray(np.asarray(poses6, np.float32).reshape(-1, 6))
+        L.check(self.lib.slio_lmap_set_key_poses(self.m, L.fptr(t), t.shape[0]), "lmap_set_key_poses")
+        self._poses6 = t.copy()
+        self.cloudKeyPoses3D[:, :3] = t[:, 3:6]
+
+    def correctPoses(self) -> None:
+        """:1769-1798: after a closed loop the recent list is cleared and every
+        key pose takes the graph's estimate (the table graph.add_loop
+        returned; the isamCurrentEstimate -> table mapping is INTEGRATION.md's)."""
+        if not self.aLoopIsClosed:
+            return
+        self.recentKeyFrames = []
+        if self._corrected is not None:
+            self.set_key_poses(self._corrected)
+            self._corrected = None
+        self.aLoopIsClosed = False
+
+    def detectLoopClosure(self) -> int:
+        """:863-887: the closest history key, or -1."""
+        xyz = np.ascontiguousarray(self.cloudKeyPoses3D[:, :3], np.float32)
+        times = np.ascontiguousarray(self.keyTimes, np.float64)
+        cur = np.ascontiguousarray(self.currentRobotPosPoint, np.float32)
+        out = C.c_int32(-1)
+        L.check(self.lib.slio_lmap_detect_loop(L.fptr(xyz), L.dptr(times), xyz.shape[0], L.fptr(cur),
+                                               float(self.timeLaserOdometry), HISTORY_KEYFRAME_SEARCH_RADIUS, 30.0,
+                                               C.byref(out)), "lmap_detect_loop")
+        return out.value
+
+    def loop_clouds(self, latest: int, closest: int, search_num: int = HISTORY_KEYFRAME_SEARCH_NUM,
+                    leaf: float = 0.4) -> np.ndarray:
+        """slio_lmap_loop_clouds: {source concatenated, source kept, target
+        concatenated, target points}."""
+        self.loop_counts = np.zeros(4, np.int64)
+        L.check(self.lib.slio_lmap_loop_clouds(self.m, latest, closest, search_num, leaf,
+                                               L.i64ptr(self.loop_counts)), "lmap_loop_clouds")
+        return self.loop_counts.copy()
+
+    def loop_correction(self, final_T, latest: int, closest: int, fitness: float):
+        """slio_lmap_loop_correction: (pose_from, pose_to, noise)."""
+        T = np.ascontiguousarray(np.asarray(final_T, np.float32).reshape(16))
+        pf, pt, noise = np.empty(6, np.float32), np.empty(6, np.float32), C.c_float()
+        a, b = np.ascontiguousarray(self._poses6[latest]), np.ascontiguousarray(self._poses6[closest])
+        L.check(self.lib.slio_lmap_loop_correction(L.fptr(T), L.fptr(a), L.fptr(b), float(fitness), L.fptr(pf),
+                                                   L.fptr(pt), C.byref(noise)), "lmap_loop_correction")
+        return pf, pt, noise.value
+
+    def performLoopClosure(self, graph=None, lockstep: Optional[bool] = None, batch: int = 0,
+                           search_num: int = HISTORY_KEYFRAME_SEARCH_NUM) -> Optional[LegoLoopClosure]:
+        """:944-1023, called between run() calls (the reference runs it in a
+        1 Hz thread under `mtx`).  None where the reference returns early: no
+        key yet, no candidate, ICP not converged or its fitness above
+        historyKeyframeFitnessScore.  The ICP (:957-971, max distance 100, 100
+        iterations, 1e-6, 1e-6) runs as slio_icp_align on the loop handle, or
+        as the lockstep loop (lockstep=True; None: the module's default).
+        With a `graph` (default: self.graph), graph.add_loop(closure) adds the
+        factor and returns the corrected key-pose table, which the next run()'s
+        correctPoses writes; without one the closure is only returned."""
+        if self.cloudKeyPoses3D.shape[0] == 0:
+            return None
+        closest = self.detectLoopClosure()
+        if closest < 0:
+            return None
+        latest = self.cloudKeyPoses3D.shape[0] - 1
+        self.loop_clouds(latest, closest, search_num)
+        if lockstep is None:
+            lockstep = LOOP_ICP_LOCKSTEP_DEFAULT
+        h = self.handle(LOOP)
+        if lockstep:
+            res = icp_align_lockstep(self.lib, h, 100.0, max_iterations=100, owner=self)
+        else:
+            res = icp_align_device(self.lib, h, 100.0, batch=batch, max_iterations=100, owner=self)
+        conv, T, fitness, iters, state = res
+        self.loop_final_T, self.loop_fitness = T, fitness
+        if not conv or fitness > float(np.float32(HISTORY_KEYFRAME_FITNESS_SCORE)):
+            return None
+        pf, pt, noise = self.loop_correction(T, latest, closest, fitness)
+        closure = LegoLoopClosure(latest, closest, pf, pt, noise, iters, state)
+        graph = self.graph if graph is None else graph
+        if graph is not None:
+            table = graph.add_loop(closure)
+            self._corrected = np.array(table, np.float32).reshape(-1, 6)
+            self.aLoopIsClosed = True
+        return closure

@@ -194,6 +194,65 @@ def _upload(lib, fn, h, pts):
     return pts.shape[0]
 
 
+DBL_MAX = float(np.finfo(np.float64).max)
+
+
+def _icp_params(lib, max_iterations=None):
+    prm = L.SlioIcpParams()
+    L.check(lib.slio_icp_params_default(C.byref(prm)), "icp params")
+    if max_iterations is not None:
+        prm.max_iterations = int(max_iterations)
+    return prm
+
+
+def icp_align_device(lib, h, max_corr_dist: float, guess=None, batch: int = 0, max_iterations=None, owner=None):
+    """slio_icp_align on handle h (map = target, scan = source): icp.align and
+    getFitnessScore with the loop on the device.  Returns (converged, final_T
+    4x4 float32, fitness, iterations, convergence_state); `owner` (optional)
+    receives icp_far_first and icp_state."""
+    prm, st = _icp_params(lib, max_iterations), L.SlioIcpState()
+    g = None if guess is None else np.ascontiguousarray(np.asarray(guess, dtype=np.float32).reshape(16))
+    fit, far = C.c_double(), C.c_int64()
+    L.check(lib.slio_icp_align(h, C.byref(prm), None if g is None else L.fptr(g), float(max_corr_dist), int(batch),
+                               C.byref(st), C.byref(fit), C.byref(far)), "icp align")
+    if owner is not None:
+        owner.icp_far_first, owner.icp_state = far.value, st
+    final_T = np.array(st.final_T, dtype=np.float32).reshape(4, 4)
+    return bool(st.converged), final_T, fit.value, int(st.iterations), int(st.convergence_state)
+
+
+def icp_align_lockstep(lib, h, max_corr_dist: float, guess=None, max_iterations=None, owner=None):
+    """The same alignment with one slio_icp_correspond launch, one readback
+    and one host slio_icp_step per iteration (ScanToMap.icp_align's loop on any
+    handle)."""
+    prm, st = _icp_params(lib, max_iterations), L.SlioIcpState()
+    g = None if guess is None else np.ascontiguousarray(np.asarray(guess, dtype=np.float32).reshape(16))
+    L.check(lib.slio_icp_state_init(C.byref(st), None if g is None else L.fptr(g)), "icp state")
+    T = np.array(st.final_T, dtype=np.float32)
+    sums, nc = np.zeros(16, np.float64), C.c_int64()
+    delta, done = np.zeros(16, np.float32), C.c_int(0)
+    from_scan, far_first = 1, 0
+    while True:
+        L.check(lib.slio_icp_correspond(h, L.fptr(T), from_scan, float(max_corr_dist), L.dptr(sums), C.byref(nc)),
+                "icp correspond")
+        if from_scan:
+            far = C.c_int64()
+            L.check(lib.slio_icp_far_queries(h, C.byref(far)), "icp far queries")
+            far_first = far.value
+        L.check(lib.slio_icp_step(L.dptr(sums), nc.value, C.byref(prm), C.byref(st), L.fptr(delta), C.byref(done)),
+                "icp step")
+        if done.value:
+            break
+        T, from_scan = delta, 0
+    final_T = np.array(st.final_T, dtype=np.float32).reshape(4, 4)
+    L.check(lib.slio_icp_correspond(h, L.fptr(np.ascontiguousarray(final_T.reshape(16))), 1, math.inf, L.dptr(sums),
+                                    C.byref(nc)), "icp fitness")
+    fitness = float(sums[15]) / nc.value if nc.value > 0 else DBL_MAX
+    if owner is not None:
+        owner.icp_far_first, owner.icp_state = far_first, st
+    return bool(st.converged), final_T, fitness, int(st.iterations), int(st.convergence_state)
+
+
 class ScanToMap:
     """kdtreeCornerFromMap / kdtreeSurfFromMap and the scan-to-map solve."""
 
@@ -359,6 +418,13 @@ class ScanToMap:
         # (getFitnessScore: the mean squared distance; no point at all reads as DBL_MAX)
         fitness = float(sums[15]) / nc.value if nc.value > 0 else float(np.finfo(np.float64).max)
         return bool(st.converged), final_T, fitness, int(st.iterations), int(st.convergence_state)
+
+    def icp_align_device(self, max_corr_dist: float, guess: Optional[np.ndarray] = None, batch: int = 0):
+        """icp_align's result from the device-resident loop (slio_icp_align):
+        the same bits with ceil(iterations / batch) + 1 host waits instead of
+        iterations + 1 (batch <= 0: the library's default).  icp_far_first as
+        icp_align; icp_state keeps the final slio_icp_state."""
+        return icp_align_device(self.lib, self.loop_handle(), max_corr_dist, guess, batch, owner=self)
 
     def perform_loop_closure(self, key_poses6, key_times, t_cur: float, loop_index_container: dict,
                              radius: float = 15.0, time_diff: float = 30.0, search_num: int = 25,

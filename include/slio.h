@@ -616,11 +616,42 @@ int slio_icp_state_init(slio_icp_state* s, const float guess[16]);
  * Otherwise prev_mse = mse, NOT_CONVERGED, *done = 0. */
 int slio_icp_step(const double sums[16], int64_t ncorr, const slio_icp_params* params,
                   slio_icp_state* state, float delta[16], int* done);
+/* The whole of icp.align plus getFitnessScore (LIO-SAM :766-780; LeGO-LOAM
+ * mapOptmization.cpp:957-975) without a host wait per iteration.  The meaning
+ * is that of the lockstep loop over the entries above: slio_icp_state_init
+ * (guess); slio_icp_correspond(final_T, from_scan = 1, max_dist);
+ * slio_icp_step; then slio_icp_correspond(delta, from_scan = 0, max_dist) and
+ * slio_icp_step until *done; at last the fitness pass slio_icp_correspond(
+ * final_T, 1, INFINITY).  Every float and double it produces equals that
+ * loop's bit for bit: the pass is the same device function with its 3x4
+ * transform read from the loop's state in device memory; the 18 entries (16
+ * sums, correspondences, far queries) are added over the workgroups' partials
+ * in ascending workgroup order starting from +0, one lane per entry, exactly
+ * as slio_icp_correspond adds them on the host; one thread then runs
+ * slio_icp_step's body (one function compiled for both sides, double division
+ * and square root correctly rounded on either).
+ * An iteration is two launches (pass, one-workgroup tail) ordered by the
+ * stream alone; no kernel waits for another workgroup.  The host enqueues
+ * `batch` iterations (batch <= 0: the library's default, 8), reads the state
+ * back once, and enqueues another batch while the loop has not ended; launches
+ * after the end return at their first instruction.  Then the fitness pass and
+ * one last read: ceil(iterations / batch) + 1 host waits per call.
+ * *out = the final state; *fitness = sums[15] / ncorr of the fitness pass
+ * (DBL_MAX without a correspondence, as getFitnessScore); *far_first = the far
+ * queries of the first pass; fitness and far_first may be NULL.  Afterwards
+ * slio_icp_get_correspondences, slio_icp_get_working and slio_icp_far_queries
+ * read the fitness pass, as they do after the lockstep loop's last call.
+ * Errors are slio_icp_correspond's, plus EINVAL for a null prm or out, all
+ * reported before any device call.  An empty scan gives NO_CORRESPONDENCES
+ * (not converged, 0 iterations) without a launch. */
+int slio_icp_align(slio_handle h, const slio_icp_params* prm, const float guess[16], double max_dist,
+                   int32_t batch, slio_icp_state* out, double* fitness, int64_t* far_first);
 
-/* ---- LeGO-LOAM mapping (src/LeGO-LOAM/LeGO-LOAM/src/mapOptmization.cpp with
- *      loopClosureEnableFlag = false, and transformFusion.cpp) ----------------
+/* ---- LeGO-LOAM mapping (src/LeGO-LOAM/LeGO-LOAM/src/mapOptmization.cpp and
+ *      transformFusion.cpp; the loopClosureEnableFlag == true parts are the
+ *      entries after slio_lmap_clear) ------------------------------------------
  * One opaque mapper owns four single-rank handles on one device and one
- * stream: SLIO_LMAP_CORNER (laserCloudCornerFromMapDS, laserCloudCornerLastDS,
+ * stream (and a fifth, SLIO_LMAP_LOOP, from the first loop-closure call on): SLIO_LMAP_CORNER (laserCloudCornerFromMapDS, laserCloudCornerLastDS,
  * cornerCloudKeyFrames), SLIO_LMAP_SURF_TOTAL (laserCloudSurfFromMapDS,
  * laserCloudSurfTotalLastDS), SLIO_LMAP_SURF (laserCloudSurfLastDS,
  * surfCloudKeyFrames) and SLIO_LMAP_OUTLIER (laserCloudOutlierLastDS,
@@ -646,7 +677,13 @@ int slio_icp_step(const double sums[16], int64_t ncorr, const slio_icp_params* p
  *    transforming it again gives the same floats.  The cache's list order,
  *    which fixes the concatenation order, is kept (the caller's key list). */
 typedef struct slio_lmap* slio_lmap_handle;
-enum { SLIO_LMAP_CORNER = 0, SLIO_LMAP_SURF_TOTAL = 1, SLIO_LMAP_SURF = 2, SLIO_LMAP_OUTLIER = 3 };
+enum {
+  SLIO_LMAP_CORNER = 0,
+  SLIO_LMAP_SURF_TOTAL = 1,
+  SLIO_LMAP_SURF = 2,
+  SLIO_LMAP_OUTLIER = 3,
+  SLIO_LMAP_LOOP = 4 /* map nearHistorySurfKeyFrameCloudDS, scan latestSurfKeyFrameCloud */
+};
 typedef struct slio_lmap_params {
   int32_t device;
   int32_t max_points;          /* capacity of every downsampled scan cloud               */
@@ -665,7 +702,7 @@ typedef struct slio_lmap_params {
 int slio_lmap_params_default(slio_lmap_params* p);
 int slio_lmap_create(slio_lmap_handle* out, const slio_lmap_params* p);
 int slio_lmap_destroy(slio_lmap_handle m);
-/* One of the four handles (SLIO_LMAP_*), for the getters this library already
+/* One of the five handles (SLIO_LMAP_*), for the getters this library already
  * has -- slio_scan_download, slio_map_download, slio_map_info,
  * slio_get_neighbors, slio_far_queries, slio_s2m_kf_info / _sizes / _get --
  * and, for tests and users without the front-end, slio_map_upload /
@@ -735,6 +772,54 @@ int slio_lmap_save_keyframe(slio_lmap_handle m, const float pose6[6], int32_t* k
 int slio_lmap_get_key_poses(slio_lmap_handle m, float* poses6, int32_t cap, int32_t* nkeys);
 /* Forget every keyframe and key pose (the stores' arenas stay allocated). */
 int slio_lmap_clear(slio_lmap_handle m);
+/* -- loop closure (loopClosureEnableFlag == true: :844-1023, :1042-1097,
+ *    :1769-1798) ---------------------------------------------------------------
+ * The ICP is slio_icp_align (or the lockstep loop over slio_icp_correspond /
+ * slio_icp_step) on the SLIO_LMAP_LOOP handle with max_dist 100, 100
+ * iterations, 1e-6, 1e-6 (:957-961); PCL's rules and the three departures
+ * stated above slio_s2m_loop_cloud hold here too.  GTSAM is absent: the factor
+ * graph is the caller's, and what it returns comes back through
+ * slio_lmap_set_key_poses.
+ *
+ * The recent-keyframe branch of extractSurroundingKeyFrames (:1042-1097) is a
+ * host key list handed to slio_lmap_extract, which may repeat keys.  The
+ * reference caches the transformed clouds of that list
+ * (recent*CloudKeyFrames) and clears the cache in correctPoses; poses change
+ * nowhere else, so transforming a key from the store with the current table
+ * gives the floats the cache holds.  The cache is not mirrored; its list
+ * order, which fixes the concatenation order, is kept.
+ *
+ * Stated departures of the loop clouds:
+ *  - transformPointCloud(cloud, pose*) (:654-687) writes cos(pose->yaw) * x;
+ *    whether that multiplies in float or in double depends on which cos the
+ *    translation unit's headers select, and nothing in the tree pins it.  The
+ *    cached-sine form of :624-652 is used: float products, the double
+ *    functions rounded to float (slio_lmap_extract's arithmetic);
+ *  - the (int)intensity >= 0 filter (:901-911) keeps every point the stores
+ *    can hold from the front-end (a VoxelGrid mean of row + col / 10000 is
+ *    never negative); the stores keep no intensity and the filter is not
+ *    applied;
+ *  - ties of the nearest neighbour and the in-voxel summation order are as
+ *    stated for slio_s2m_loop_cloud and at the head of this section. */
+/* correctPoses' device side (:1775-1794): replaces the mapper's key-pose
+ * table (cloudKeyPoses6D as {rx, ry, rz, tx, ty, tz} per key), which
+ * slio_lmap_extract and slio_lmap_loop_clouds read.  EINVAL unless nkeys
+ * equals the table's length. */
+int slio_lmap_set_key_poses(slio_lmap_handle m, const float* poses6, int32_t nkeys);
+/* detectLoopClosure's cloud work (:889-931).  Source: key `latest`'s corner
+ * cloud, then its surf cloud, at its pose, concatenated and NOT downsampled,
+ * becomes the loop handle's scan (ECAPACITY beyond max_points).  Target: keys
+ * closest - search_num .. closest + search_num, skipping k < 0 and
+ * k > latest (:916-918; a target that contains `latest` itself is reproduced),
+ * for each key corner then surf, concatenated and passed through the
+ * VoxelGrid with edge `leaf` (downSizeFilterHistoryKeyFrames, 0.4, :269)
+ * under slio_scan_upload_voxel's semantics, becomes the loop handle's map,
+ * indexed as slio_map_upload would.  No point travels to the host.  counts =
+ * {source concatenated, source kept, target concatenated, target points}.
+ * EINVAL for a key out of range, search_num < 0 or a leaf that is not
+ * positive, before any device call. */
+int slio_lmap_loop_clouds(slio_lmap_handle m, int32_t latest, int32_t closest, int32_t search_num,
+                          float leaf, int64_t counts[4]);
 /* -- host only, callable without a GPU -- */
 /* transformAssociateToMap (mapOptmization.cpp:394-519; transformFusion.cpp
  * :91-215 is the same formula writing transformMapped): float arithmetic in
@@ -764,6 +849,31 @@ int slio_lmap_fuse(slio_lmap_fusion* f, const float transform_sum[6], const floa
  * `distance` (the reference's double 0.3). */
 int slio_lmap_keyframe_decision(const float prev_pos[3], const float cur_pos[3], int32_t nkeys,
                                 double distance, int* save);
+/* detectLoopClosure's search (:863-887): among the keys (key_xyz nkeys x 3 =
+ * cloudKeyPoses3D, key_time = cloudKeyPoses6D.time) whose float squared
+ * distance (dx dx + dy dy) + dz dz to cur_pos (currentRobotPosPoint) is below
+ * radius^2 (historyKeyframeSearchRadius, 5.0, utility.h:94), taken in
+ * ascending distance, equal distances by lower key, the first with
+ * |key_time - t| > time_diff (30.0, double) is *closest; -1 when there is
+ * none. */
+int slio_lmap_detect_loop(const float* key_xyz, const double* key_time, int32_t nkeys,
+                          const float cur_pos[3], double t, float radius, double time_diff,
+                          int32_t* closest);
+/* performLoopClosure after the ICP (:992-1012), float affine arithmetic in
+ * the reference's order.  final_T: the ICP's camera-frame result, row-major
+ * 4x4.  (x, y, z, roll, pitch, yaw) = pcl::getTranslationAndEulerAngles of it
+ * (roll = atan2(t21, t22), pitch = asin(-t20), yaw = atan2(t10, t00));
+ * correctionLidarFrame = pcl::getTransformation(z, x, y, yaw, roll, pitch);
+ * tWrong = getTransformation(tz, tx, ty, rz, rx, ry) of latest_pose6 = {rx,
+ * ry, rz, tx, ty, tz} (:1032-1036); tCorrect = correctionLidarFrame * tWrong
+ * as an affine product (linear part L1 L2, translation L1 t2 + t1, every sum
+ * in index order).  pose_from = {x, y, z, roll, pitch, yaw} of tCorrect;
+ * pose_to = closest_pose6 as {tz, tx, ty, rz, rx, ry} (:1025-1030); *noise =
+ * (float)fitness (:1009).  poseFrom.between(poseTo) and the factor are the
+ * caller's GTSAM. */
+int slio_lmap_loop_correction(const float final_T[16], const float latest_pose6[6],
+                              const float closest_pose6[6], double fitness, float pose_from[6],
+                              float pose_to[6], float* noise);
 /* The M x N QR of slio_cvsolve.hpp for tests: (m, n) in {(5, 3), (3, 3),
  * (6, 6)}; returns 1 where the solve gives up (x zeroed). */
 int slio_lmap_qr_solve(int m, int n, const float* A, const float* b, float* x);

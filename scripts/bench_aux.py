@@ -13,7 +13,13 @@
   s2m_loop  one LIO-SAM loop closure (loopFindNearKeyframes twice + ICP + fitness)
             on the device: 51 keyframes in the store, the source keyframe's pose
             off by 1 m and 3 deg, against a host restatement (scipy cKDTree +
-            numpy) over the same clouds (only when named)
+            numpy) over the same clouds, and the same ICP through the
+            device-resident loop (icp_align_device) (only when named)
+  lego_loop one LeGO-LOAM loop closure (LegoMapping(loop_closure=True)): 60 keyframes
+            of the 16 x 1800 sequence's sizes in the stores, the newest key's pose
+            off by 1 m and 3 deg; both assemblies, the ICP through slio_icp_align
+            (per batch size) and through the lockstep loop on the same clouds, the
+            fitness pass, the host restatement beside them (only when named)
   lego_odom LeGO-LOAM front-end + scan-to-scan odometry on a 16 x 1800 sequence:
             sweeps per second, the odometry call alone, the lockstep loop and
             the numpy restatement (only when named)
@@ -276,6 +282,38 @@ def s2m_map(n_kf=50, n_surf=20000, n_corner=1000, reps=200):
     s.close()
 
 
+def host_icp(src, tgt, max_dist):
+    """The ICP restated on the host over the two clouds: scipy cKDTree (built
+    once, one query per pass, all cores) + numpy sums + the numpy Umeyama of
+    tests/icp_model.py."""
+    import icp_model as M
+    from scipy.spatial import cKDTree
+    med = lambda v: float(np.median(v))  # noqa: E731
+    t0 = time.perf_counter()
+    tree = cKDTree(tgt.astype(np.float64))
+    t_build = (time.perf_counter() - t0) * 1e3
+    st = M.State()
+    work, pass_ms = src.copy(), []
+
+    def one_pass(w, md):
+        d, j = tree.query(w.astype(np.float64), k=1, workers=-1)
+        ok = d <= md
+        p, q = w[ok].astype(np.float64), tgt[j[ok]].astype(np.float64)
+        sums = np.concatenate([p.sum(0), q.sum(0), (q.T @ p).reshape(9), [(d[ok] * d[ok]).sum()]])
+        return sums, int(ok.sum())
+    while True:
+        t1 = time.perf_counter()
+        sums, n = one_pass(work, max_dist)
+        pass_ms.append((time.perf_counter() - t1) * 1e3)
+        delta, done = M.step(sums, n, st)
+        if done:
+            break
+        work = M.transform32(delta, work)
+    sums, n = one_pass(M.transform32(st.final_T, src), np.inf)
+    return dict(ms_total=(time.perf_counter() - t0) * 1e3, ms_tree_build=t_build, ms_per_pass=med(pass_ms),
+                iterations=st.iterations, fitness=sums[15] / max(n, 1))
+
+
 def s2m_loop(n_kf=51, n_surf=20000, n_corner=1000, reps=5):
     """performLoopClosure's device work: the store holds n_kf keyframes (as
     s2m_map's) plus the newest one, a fresh draw at keyframe 25's place whose
@@ -288,7 +326,6 @@ def s2m_loop(n_kf=51, n_surf=20000, n_corner=1000, reps=5):
     tests/icp_model.py.  far_start: one more first pass with the source 12 m
     off, where most queries take the far path."""
     import icp_model as M
-    from scipy.spatial import cKDTree
     from agi_lidar_slam_amd import _lib as L, synth
     from agi_lidar_slam_amd.lio_sam import ScanToMap
     pr = synth.make_s2m_problem()
@@ -344,32 +381,19 @@ def s2m_loop(n_kf=51, n_surf=20000, n_corner=1000, reps=5):
                                   C.byref(got)), "map_download")
     tgt = np.stack(xt, 1)
 
-    def host_icp():
-        t0 = time.perf_counter()
-        tree = cKDTree(tgt.astype(np.float64))
-        t_build = (time.perf_counter() - t0) * 1e3
-        st = M.State()
-        work, pass_ms = src.copy(), []
-
-        def one_pass(w, max_dist):
-            d, j = tree.query(w.astype(np.float64), k=1, workers=-1)
-            ok = d <= max_dist
-            p, q = w[ok].astype(np.float64), tgt[j[ok]].astype(np.float64)
-            sums = np.concatenate([p.sum(0), q.sum(0), (q.T @ p).reshape(9), [(d[ok] * d[ok]).sum()]])
-            return sums, int(ok.sum())
-        while True:
-            t1 = time.perf_counter()
-            sums, n = one_pass(work, 30.0)
-            pass_ms.append((time.perf_counter() - t1) * 1e3)
-            delta, done = M.step(sums, n, st)
-            if done:
-                break
-            work = M.transform32(delta, work)
-        sums, n = one_pass(M.transform32(st.final_T, src), np.inf)
-        return dict(ms_total=(time.perf_counter() - t0) * 1e3, ms_tree_build=t_build, ms_per_pass=med(pass_ms),
-                    iterations=st.iterations, fitness=sums[15] / max(n, 1))
-    host_icp()
-    host = host_icp()
+    host_icp(src, tgt, 30.0)
+    host = host_icp(src, tgt, 30.0)
+    # the same ICP through the device-resident loop (slio_icp_align), per batch size
+    dev_loop = {}
+    for batch in (0, 1, 4, 8, 16, 32):
+        s.icp_align_device(30.0, batch=batch)
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            rd = s.icp_align_device(30.0, batch=batch)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        dev_loop["default" if batch == 0 else str(batch)] = med(ts)
+    same = bool(rd[0] == res[0] and np.array_equal(rd[1], res[1]) and rd[2:] == res[2:])
     # a far start: the source 12 m off (the first pass only)
     shift = np.eye(4, dtype=np.float32)
     shift[:3, 3] = [12.0, -9.0, 0.0]
@@ -389,7 +413,137 @@ def s2m_loop(n_kf=51, n_surf=20000, n_corner=1000, reps=5):
         "far_share_first_pass": rows[-1][5] / max(n_src, 1),
         "far_start": {"shift_m": 15.0, "far_share": far.value / max(n_src, 1), "ms_pass": med(tf[1:])},
         "host_ckdtree_numpy": host}), flush=True)
+    print(json.dumps({
+        "bench": "lio_sam_s2m_loop_closure_icp_align_device", "iterations": rd[3], "convergence_state": rd[4],
+        "ms_icp_incl_fitness_by_batch": dev_loop, "ms_lockstep_icp_incl_fitness": med([r[3] for r in rows]),
+        "host_waits_lockstep": res[3] + 1, "same_bits_as_lockstep": same}), flush=True)
     s.close()
+
+
+def lego_loop(n_kf=60, n_corner=246, n_surf=2000, n_outlier=1000, reps=5):
+    """performLoopClosure on LegoMapping(loop_closure=True).  The stores hold
+    n_kf keyframes of about the sizes the 16 x 1800 sequence leaves (lego_map:
+    246 corner, ~3,000 surf + outlier per key), drawn from make_s2m_problem's
+    maps in the camera frame, on a circle of 0.5 m steps, 1 s apart; the newest
+    key lies beside key 0 and its stored pose is off by 1 m and 3 deg of yaw.
+    detectLoopClosure picks key 0; the target is keys 0..25
+    (historyKeyframeSearchNum 25, clipped at 0), the source the newest key,
+    not downsampled.  The ICP (100 m, 100 iterations) runs through
+    slio_icp_align at several batch sizes and through the lockstep loop on the
+    same clouds; the host figure restates the ICP as s2m_loop's does."""
+    import math
+    import lego_map_model as M
+    from agi_lidar_slam_amd import _lib as L, synth
+    from agi_lidar_slam_amd.lego_map import CORNER, LOOP, OUTLIER, SURF, LegoMapping
+    from agi_lidar_slam_amd.lio_sam import icp_align_device, icp_align_lockstep
+    pr = synth.make_s2m_problem()
+    pools = [M.cam_points(pr["corner_map"]), M.cam_points(pr["surf_map"]), M.cam_points(pr["surf_map"])]
+    rng = np.random.default_rng(12)
+    mp = LegoMapping(max_points=20000, loop_closure=True)
+    lib = mp.lib
+    radius = 0.5 * n_kf / (2.0 * math.pi)
+
+    def pose_of(k):
+        th = 2.0 * math.pi * k / n_kf
+        return np.array([0.004 * math.sin(th), 0.5 * math.pi - th, -0.003 * math.cos(th), radius * math.cos(th),
+                         0.01 * k, radius * math.sin(th)], np.float32)
+
+    def to_sensor(pose, pw):   # the inverse of M.to_map, in double
+        rx, ry, rz, tx, ty, tz = (float(v) for v in pose)
+        q = pw.astype(np.float64) - np.array([tx, ty, tz])
+        cr, sr, cp, sp, cy, sy = (math.cos(rx), math.sin(rx), math.cos(ry), math.sin(ry), math.cos(rz),
+                                  math.sin(rz))
+        x2, z2, y2 = cp * q[:, 0] - sp * q[:, 2], sp * q[:, 0] + cp * q[:, 2], q[:, 1]
+        y1, z1 = cr * y2 + sr * z2, -sr * y2 + cr * z2
+        return np.column_stack([cy * x2 + sy * y1, -sy * x2 + cy * y1, z1]).astype(np.float32)
+
+    for k in range(n_kf):
+        true = pose_of(k)
+        stored = true.copy()
+        if k == n_kf - 1:
+            stored = (stored + np.array([0, np.deg2rad(3.0), 0, 0.8, 0.0, -0.6], np.float32)).astype(np.float32)
+        for which, pool, n in zip((CORNER, SURF, OUTLIER), pools, (n_corner, n_surf, n_outlier)):
+            w = pool[rng.choice(pool.shape[0], n)] + rng.normal(0, 0.05, (n, 3))
+            c = to_sensor(true, w)
+            x, y, z = (np.ascontiguousarray(c[:, a]) for a in range(3))
+            L.check(lib.slio_scan_upload(mp.handle(which), L.fptr(x), L.fptr(y), L.fptr(z), n), "scan_upload")
+        mp._tobe, mp._aft, mp.timeLaserOdometry = stored.copy(), stored.copy(), float(k)
+        assert mp.saveKeyFramesAndFactor()
+    latest = n_kf - 1
+    closest = mp.detectLoopClosure()
+    med = lambda v: float(np.median(v))  # noqa: E731
+    mp.loop_clouds(latest, closest)
+    t_asm = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        cnt = mp.loop_clouds(latest, closest)
+        t_asm.append((time.perf_counter() - t0) * 1e3)
+    h = mp.handle(LOOP)
+
+    class Own:
+        pass
+    own = Own()
+    icp_align_lockstep(lib, h, 100.0, max_iterations=100, owner=own)
+    t_lock = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        rl = icp_align_lockstep(lib, h, 100.0, max_iterations=100, owner=own)
+        t_lock.append((time.perf_counter() - t0) * 1e3)
+    far_first = own.icp_far_first
+    dev_loop, waits = {}, {}
+    for batch in (0, 1, 2, 4, 8, 16, 32, 100):
+        icp_align_device(lib, h, 100.0, batch=batch, max_iterations=100)
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            rd = icp_align_device(lib, h, 100.0, batch=batch, max_iterations=100, owner=own)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        name = "default" if batch == 0 else str(batch)
+        dev_loop[name] = med(ts)
+        if batch:
+            waits[name] = -(-rd[3] // batch) + 1
+    same = bool(rd[0] == rl[0] and np.array_equal(rd[1], rl[1]) and rd[2:] == rl[2:] and
+                own.icp_far_first == far_first)
+    # the fitness pass alone
+    sums, nc = np.zeros(16), C.c_int64()
+    T = np.ascontiguousarray(rl[1].reshape(16))
+    t_fit = []
+    for _ in range(reps + 1):
+        t0 = time.perf_counter()
+        L.check(lib.slio_icp_correspond(h, L.fptr(T), 1, np.inf, L.dptr(sums), C.byref(nc)), "icp fitness")
+        t_fit.append((time.perf_counter() - t0) * 1e3)
+    # the whole call, both ICP paths
+    mp.currentRobotPosPoint = mp.cloudKeyPoses3D[latest, :3].copy()
+    t_call = {}
+    for name, lockstep in (("device", False), ("lockstep", True)):
+        mp.performLoopClosure(lockstep=lockstep)
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            cl = mp.performLoopClosure(lockstep=lockstep)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        t_call[name] = med(ts)
+    n_src, n_tgt = int(cnt[1]), int(cnt[3])
+    xs = [np.zeros(n_src, np.float32) for _ in range(3)]
+    L.check(lib.slio_scan_download(h, *(L.fptr(a) for a in xs)), "scan_download")
+    xt = [np.zeros(n_tgt, np.float32) for _ in range(3)]
+    ids, got = np.zeros(n_tgt, np.uint32), C.c_int64()
+    L.check(lib.slio_map_download(h, *(L.fptr(a) for a in xt), ids.ctypes.data_as(C.POINTER(C.c_uint32)), n_tgt,
+                                  C.byref(got)), "map_download")
+    src, tgt = np.stack(xs, 1), np.stack(xt, 1)
+    host_icp(src, tgt, 100.0)
+    host = host_icp(src, tgt, 100.0)
+    print(json.dumps({
+        "bench": "lego_loop_closure", "keyframes": n_kf, "points_per_keyframe": [n_corner, n_surf, n_outlier],
+        "latest": latest, "closest": int(closest), "source_points": n_src, "target_concatenated": int(cnt[2]),
+        "target_points": n_tgt, "ms_two_assemblies": med(t_asm),
+        "iterations": rl[3], "convergence_state": rl[4], "converged": rl[0], "fitness": rl[2],
+        "far_queries_first_pass": far_first, "ms_fitness_pass": med(t_fit[1:]),
+        "ms_icp_lockstep_incl_fitness": med(t_lock), "host_waits_lockstep": rl[3] + 1,
+        "ms_icp_align_by_batch": dev_loop, "host_waits_by_batch": waits, "same_bits_as_lockstep": same,
+        "ms_perform_loop_closure": t_call, "closure_found": cl is not None,
+        "host_ckdtree_numpy": host, "kernel_times": "not measured"}), flush=True)
+    mp.close()
 
 
 def lego_odom(sweeps=12, restate=True):
@@ -704,6 +858,8 @@ if __name__ == "__main__":
         lego_map()
     if "lego_odom" in what:
         lego_odom()
+    if "lego_loop" in what:
+        lego_loop()
     if "s2m_loop" in what:
         s2m_loop()
     if "s2m_map" in what:
