@@ -225,6 +225,17 @@ class SlioLregParams(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
+class SlioAloamParams(C.Structure):
+    """slio_aloam_params (include/slio_frontend.h)."""
+    _fields_ = [("device", C.c_int32), ("n_scans", C.c_int32), ("max_points", C.c_int32), ("reserved0", C.c_int32),
+                ("minimum_range", C.c_double), ("scan_period", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class SlioAloamView(C.Structure):
+    """slio_aloam_view (include/slio_frontend.h)."""
+    _fields_ = [("cloud", C.c_void_p * 5), ("count", C.c_int32 * 5), ("device", C.c_int32)]
+
+
 class SlioLmapParams(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("leaf_corner", C.c_float),
                 ("leaf_surf", C.c_float), ("leaf_outlier", C.c_float), ("pose_leaf", C.c_float),
@@ -426,6 +437,18 @@ SIGNATURES = {
     "slio_lreg_chain_tile": (C.c_int, [_IP, _IP]),
     "slio_lreg_classify_host": (C.c_int, [_FP, C.c_int64, _IP, _U8P, _FP, _FP, _FP, _IP, _IP]),
     "slio_lreg_plane_judge": (C.c_int, [_FP, C.c_int32, C.c_int32, _IP]),
+    # include/slio_frontend.h (A-LOAM scanRegistration)
+    "slio_aloam_params_default": (C.c_int, [C.POINTER(SlioAloamParams)]),
+    "slio_aloam_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioAloamParams)]),
+    "slio_aloam_destroy": (C.c_int, [_P]),
+    "slio_aloam_run": (C.c_int, [_P, _FP, C.c_int64, _IP]),
+    "slio_aloam_get_cloud": (C.c_int, [_P, C.c_int, _FP, C.c_int64]),
+    "slio_aloam_get_scan_index": (C.c_int, [_P, _IP, _IP]),
+    "slio_aloam_get_work": (C.c_int, [_P, _FP, _IP, _U8P]),
+    "slio_aloam_get_view": (C.c_int, [_P, C.POINTER(SlioAloamView)]),
+    "slio_aloam_tile": (C.c_int, [_IP, _IP]),
+    "slio_aloam_register_host": (C.c_int, [C.POINTER(SlioAloamParams), _FP, C.c_int64, _FP, _FP, _FP, _FP, _FP, _IP,
+                                           _IP, _FP, _IP, _U8P, _IP, _IP]),
 }
 
 _lib = None

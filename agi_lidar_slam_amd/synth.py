@@ -410,6 +410,35 @@ def make_vlp16_sweep(seed: int = 20261015, horizon: int = 1800, yaw_rate: float 
                 z=np.ascontiguousarray(pts[:, 2]), time_scan_cur=time_scan_cur, imu=imu)
 
 
+def make_spinning_sweep(elevations_deg, horizon: int = 1800, seed: int = 20261015, yaw_rate: float = 0.3,
+                        dropout: float = 0.03, n_map_scene: int = 2_000_000) -> dict:
+    """One sweep of a spinning LiDAR with any beam table, as make_vlp16_sweep
+    makes it for the VLP-16: firing order (every beam of elevations_deg per
+    azimuth step), clockwise, the same scene, sensor pose, noise and dropout.
+    With elevations_deg = -15, -13 .. 15 the points are make_vlp16_sweep's."""
+    elev = np.asarray(elevations_deg, np.float64).reshape(-1)
+    nb = elev.size
+    scene = make_scene(seed, n_map_scene)
+    rng = np.random.default_rng(seed + 4)
+    yaw0 = rng.uniform(-np.pi, np.pi)
+    org = np.array([rng.uniform(-3, 3), rng.uniform(-3, 3), 1.7])
+    cols = np.repeat(np.arange(horizon), nb)
+    rings = np.tile(np.arange(nb), horizon)
+    t = cols * (0.1 / horizon)
+    az = -(cols + rng.uniform(-0.3, 0.3, cols.size)) * (2 * np.pi / horizon) + np.pi  # clockwise
+    el = np.deg2rad(elev[rings] + rng.normal(0, 0.02, cols.size))
+    dl = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], 1)
+    yaw = yaw0 + yaw_rate * t
+    cy, sy = np.cos(yaw), np.sin(yaw)
+    dw = np.stack([cy * dl[:, 0] - sy * dl[:, 1], sy * dl[:, 0] + cy * dl[:, 1], dl[:, 2]], 1)
+    r = _cast(scene, org, dw, 100.0)
+    ok = np.isfinite(r) & (rng.uniform(size=cols.size) >= dropout)
+    r = r + rng.normal(0.0, 0.01, cols.size)
+    pts = (dl[ok] * r[ok, None]).astype(np.float32)
+    return dict(x=np.ascontiguousarray(pts[:, 0]), y=np.ascontiguousarray(pts[:, 1]),
+                z=np.ascontiguousarray(pts[:, 2]), ring=rings[ok].astype(np.int32), col=cols[ok].astype(np.int32))
+
+
 def s2m_lidar_pose(fr):
     """LIO-SAM's transformTobeMapped (roll, pitch, yaw, x, y, z) of a frame's
     ground-truth LiDAR pose, with its rotation matrix and translation."""

@@ -399,6 +399,112 @@ int slio_lreg_classify_host(const float* xyzi, int64_t n, int32_t* flags, uint8_
 /* plane_judge (:64-120) on xyz[num * 3], 1 <= num <= 64. */
 int slio_lreg_plane_judge(const float* xyz, int32_t num, int32_t threshold, int32_t* is_plane);
 
+/* ======================================================================
+ * A-LOAM scanRegistration (src/A-LOAM/src/scanRegistration.cpp; every
+ * path:line below is in that file): laserCloudHandler :124-432 on the device
+ * for the 16-, 32- and 64-line layouts.  One opaque handle owns the buffers of
+ * one device and one stream.  Input: n x {x, y, z} float32 in the message's
+ * order.  A run is
+ *   filters    :145-148  non-finite points and points nearer than
+ *                        minimum_range dropped, order kept
+ *   scan id    :155-239  startOri / endOri from the first and last survivor,
+ *                        the scan id from the elevation, the two orientation
+ *                        branches, intensity = scanID + scanPeriod * relTime
+ *   bucketing  :246-250  laserCloud = the scans concatenated, stable
+ *   curvature  :254-278  the 11-tap stencil over the concatenated cloud
+ *   picks      :289-422  per scan, six sectors: 2 sharp, up to 20 less sharp,
+ *                        up to 4 flat, +-5 neighbour marks up to a 0.05 gap
+ *   VoxelGrid  :424-431  one per scan over its less-flat points, leaf 0.2
+ * as seven launches, whatever n, on one stream and ONE host wait, the copy of
+ * the five counts.  The five clouds stay on the device (slio_aloam_get_view)
+ * until the next run.  halfPassed (:166) is no serial dependency: until it is
+ * set every kept point is evaluated in the first branch, so the switch point
+ * is the first kept point whose first-branch `ori - startOri > M_PI`, a
+ * min-reduction; points up to and including it use the first branch.
+ *
+ * Stated departures from the reference:
+ *  - std::sort (:304) orders equal curvatures as introsort leaves them; here
+ *    the sort is stable, ties by position;
+ *  - atan2 of two floats is the double function rounded to float (the
+ *    library's convention); atan(z / sqrt(..)) (:177) is the double function
+ *    of the float quotient, `* 180 / M_PI` in double, rounded to float on
+ *    assignment.  Which overload the reference's unqualified atan binds to
+ *    depends on its headers; the scan id differs only for a point whose
+ *    pre-truncation scan value lies within rounding of an integer;
+ *  - an input with no survivor gives five empty clouds (the reference reads
+ *    points[0] of an empty cloud, :155);
+ *  - a NaN elevation (a point at the origin with minimum_range 0) is dropped;
+ *    non-finite curvature (coordinates near float overflow) is outside the
+ *    contract: it sorts by its bit pattern and faults nothing;
+ *  - inside a voxel the points are summed in list order (as the LeGO
+ *    front-end's per-ring VoxelGrid, slio_lio_*);
+ *  - PUB_EACH_LINE (:469-477) and systemDelay (:61, 0) are not restated.
+ * Errors as in slio.h; argument errors are reported before any device call.
+ * ====================================================================== */
+typedef struct slio_aloam* slio_aloam_handle;
+
+typedef struct slio_aloam_params {
+  int32_t device;
+  int32_t n_scans;    /* 16, 32 or 64 (scan_line, :487) */
+  int32_t max_points; /* input capacity, 1 .. 400000 = cloudCurvature's size (:65-68) */
+  int32_t reserved0;
+  double minimum_range; /* 0.1 (:82); compared as a float (:93, :148) */
+  double scan_period;   /* 0.1 (:59) */
+  int32_t reserved[4];
+} slio_aloam_params;
+
+/* The device-resident result of the last run: device pointers to the five
+ * clouds (n x {x, y, z, intensity}) in the order laserCloud, cornerPointsSharp,
+ * cornerPointsLessSharp, surfPointsFlat, surfPointsLessFlat (:437-465), valid
+ * until the next run or destroy. */
+typedef struct slio_aloam_view {
+  const float* cloud[5];
+  int32_t count[5];
+  int32_t device;
+} slio_aloam_view;
+
+/* device 0, n_scans 16, max_points 400000, minimum_range 0.1, scan_period 0.1. */
+int slio_aloam_params_default(slio_aloam_params* p);
+/* EINVAL: n_scans not 16 / 32 / 64, max_points outside 1 .. 400000, negative
+ * device (before any device call), no such device. */
+int slio_aloam_create(slio_aloam_handle* out, const slio_aloam_params* p);
+int slio_aloam_destroy(slio_aloam_handle h);
+/* laserCloudHandler (:124-432) on xyz[n * 3].  counts = sizes of the five
+ * clouds in the view's order.  EINVAL: n < 0, null cloud with n > 0, null
+ * counts; ECAPACITY: n > max_points. */
+int slio_aloam_run(slio_aloam_handle h, const float* xyz, int64_t n, int32_t counts[5]);
+/* Cloud `kind` (0 .. 4, the view's order) of the last run: counts[kind] x 4.
+ * ESTATE without a run; ECAPACITY when cap < counts[kind]. */
+int slio_aloam_get_cloud(slio_aloam_handle h, int kind, float* xyzi, int64_t cap);
+/* scanStartInd / scanEndInd (:246-250), n_scans entries each. */
+int slio_aloam_get_scan_index(slio_aloam_handle h, int32_t* start, int32_t* end);
+/* For tests: cloudCurvature, cloudLabel, cloudNeighborPicked over [0,
+ * counts[0]) (:274-277; 0 where the reference's loop does not write).  Any
+ * may be NULL. */
+int slio_aloam_get_work(slio_aloam_handle h, float* curvature, int32_t* label, uint8_t* picked);
+/* The device view of the last run; waits for the handle's stream. */
+int slio_aloam_get_view(slio_aloam_handle h, slio_aloam_view* v);
+/* The kernels' shape: points per workgroup of the per-point passes, and the
+ * longest list (a sector, or a scan's less-flat list) the LDS sort takes in
+ * one piece; a longer one is sorted in pieces and merged in global memory. */
+int slio_aloam_tile(int32_t* block, int32_t* sort_cap);
+/* -- host only, callable without a GPU -- */
+/* The whole handler as its literal serial loops (p->device is not read).
+ * Clouds sized for n points, scan_start / scan_end for n_scans entries,
+ * curvature / label / picked for n; any output but counts may be NULL.
+ * stats[18] = points dropped as non-finite, by range (:102), by scan id
+ * (:184, :190, :201), of those by `scanID > 50` alone; endOri -= 2 pi (:160),
+ * += 2 pi (:162); first branch += 2 pi (:216), -= 2 pi (:218); second branch
+ * += 2 pi (:228), -= 2 pi (:230); halfPassed set (:222); scans skipped
+ * (:291); 21st-candidate breaks (:332); flat points (:377); 4th-flat breaks
+ * (:383); marks written outside the sector of their pick; candidates that
+ * pass the curvature test but carry a mark of another sector; scans whose
+ * VoxelGrid takes PCL's overflow branch. */
+int slio_aloam_register_host(const slio_aloam_params* p, const float* xyz, int64_t n, float* laser_cloud,
+                             float* corner_sharp, float* corner_less_sharp, float* surf_flat,
+                             float* surf_less_flat, int32_t* scan_start, int32_t* scan_end, float* curvature,
+                             int32_t* label, uint8_t* picked, int32_t counts[5], int32_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

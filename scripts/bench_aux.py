@@ -32,6 +32,9 @@
             call and its split (select + gather, downsample, optimise, update),
             iterations, map and cube sizes, host waits, the last call once more
             through the host restatement (only when named)
+  aloam_reg A-LOAM's scanRegistration (AloamScanRegistration: slio_aloam_*) on a VLP-16
+            sweep (horizon 1800) and a 64-line sweep (horizon 2083): ms per registration,
+            the five counts, the host restatement beside it (only when named)
   livox_reg livox_mapping's scanRegistration (LivoxScanRegistration: slio_lreg_*) on a
             dense continuous-curve frame of about 24,000 returns: ms per registration,
             the counts, the host restatement beside it; then process_cloud (sensor's
@@ -848,8 +851,41 @@ def livox_reg(n_rays=31000, frames_n=8, reps=20):
         h.close()
 
 
+def aloam_reg(reps=20):
+    """A-LOAM's scanRegistration (AloamScanRegistration: slio_aloam_*) on a
+    VLP-16 sweep at horizon 1800 and a 64-line sweep at horizon 2083
+    (synth.make_spinning_sweep): ms per registration (the upload, seven
+    launches and the wait for the counts; host wall clock around the
+    synchronous call, mean of `reps` after a warm-up), the five counts, and
+    the same input through the host restatement (slio_aloam_register_host, one
+    thread) beside it."""
+    from agi_lidar_slam_amd import synth
+    from agi_lidar_slam_amd.aloam import CLOUDS, AloamScanRegistration, register_host
+    upper, lower = 2.0 - np.arange(33) / 3.0, -8.83 - np.arange(1, 32) / 2.0
+    inputs = (("vlp16_h1800", 16, -15.0 + 2.0 * np.arange(16), 1800),
+              ("hdl64_h2083", 64, np.concatenate([upper, lower]), 2083))
+    rows = []
+    for name, n_scans, beams, horizon in inputs:
+        sw = synth.make_spinning_sweep(beams, horizon=horizon)
+        xyz = np.ascontiguousarray(np.stack([sw["x"], sw["y"], sw["z"]], 1), np.float32)
+        reg = AloamScanRegistration(n_scans=n_scans)
+        reg.run(xyz)                                     # warm-up
+        ms_reg, counts = t_ms(lambda: reg.run(xyz), reps)
+        ms_host, host = t_ms(lambda: register_host(xyz, n_scans=n_scans), 3)
+        got = reg.laserCloudHandler(xyz)
+        same = all(np.array_equal(got[k].view(np.uint32), host[k].view(np.uint32)) for k in CLOUDS)
+        rows.append({"input": name, "points": int(len(xyz)), "ms_per_registration": ms_reg,
+                     "counts": [int(v) for v in counts], "ms_host_restatement": ms_host,
+                     "host_same_bits_as_device": bool(same)})
+        reg.close()
+    print(json.dumps({"bench": "aloam_reg", "inputs": rows, "launches_per_registration": 7,
+                      "host_waits_per_registration": 1, "kernel_times": "not measured"}), flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "aloam_reg" in what:
+        aloam_reg()
     if "livox_reg" in what:
         livox_reg()
     if "livox_map" in what:
