@@ -236,6 +236,48 @@ class SlioAloamView(C.Structure):
     _fields_ = [("cloud", C.c_void_p * 5), ("count", C.c_int32 * 5), ("device", C.c_int32)]
 
 
+class SlioAloamOdomParams(C.Structure):
+    """slio_aloam_odom_params (include/slio_frontend.h)."""
+    _fields_ = [("device", C.c_int32), ("n_scans", C.c_int32), ("max_points", C.c_int32),
+                ("skip_frame_num", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class SlioAloamOdomPass(C.Structure):
+    """slio_aloam_odom_pass (include/slio_frontend.h)."""
+    _fields_ = [("corner", C.c_int32), ("plane", C.c_int32), ("degenerate", C.c_int32), ("iterations", C.c_int32),
+                ("accepted", C.c_int32), ("outliers", C.c_int32), ("stop", C.c_int32), ("few", C.c_int32),
+                ("cost_first", C.c_double), ("cost_last", C.c_double), ("it_q", C.c_double * 4 * 4),
+                ("it_t", C.c_double * 3 * 4), ("it_cost", C.c_double * 4), ("it_mu", C.c_double * 4)]
+
+
+class SlioAloamOdomResult(C.Structure):
+    """slio_aloam_odom_result (include/slio_frontend.h)."""
+    _fields_ = [("q_w_curr", C.c_double * 4), ("t_w_curr", C.c_double * 3), ("q_last_curr", C.c_double * 4),
+                ("t_last_curr", C.c_double * 3), ("inited", C.c_int32), ("published", C.c_int32),
+                ("frame_count", C.c_int32), ("reserved", C.c_int32), ("passes", SlioAloamOdomPass * 2)]
+
+
+class SlioAloamOdomState(C.Structure):
+    """slio_aloam_odom_state (include/slio_frontend.h)."""
+    _fields_ = [("q_w_curr", C.c_double * 4), ("t_w_curr", C.c_double * 3), ("para_q", C.c_double * 4),
+                ("para_t", C.c_double * 3), ("inited", C.c_int32), ("frame_count", C.c_int32)]
+
+
+class SlioAloamOdomLm(C.Structure):
+    """slio_aloam_odom_lm (include/slio_frontend.h)."""
+    _fields_ = [("mu", C.c_double), ("nu", C.c_double), ("q", C.c_double * 4), ("t", C.c_double * 3),
+                ("A", C.c_double * 21), ("g", C.c_double * 6), ("cost", C.c_double), ("delta", C.c_double * 6),
+                ("model", C.c_double), ("xnorm", C.c_double), ("qn", C.c_double * 4), ("tn", C.c_double * 3),
+                ("pivots_ok", C.c_int32), ("iterations", C.c_int32), ("accepted", C.c_int32), ("stop", C.c_int32),
+                ("done", C.c_int32), ("last_accepted", C.c_int32)]
+
+
+class SlioAloamOdomView(C.Structure):
+    """slio_aloam_odom_view (include/slio_frontend.h)."""
+    _fields_ = [("corner_last", C.c_void_p), ("surf_last", C.c_void_p), ("n_corner", C.c_int32),
+                ("n_surf", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SlioLmapParams(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("leaf_corner", C.c_float),
                 ("leaf_surf", C.c_float), ("leaf_outlier", C.c_float), ("pose_leaf", C.c_float),
@@ -449,6 +491,28 @@ SIGNATURES = {
     "slio_aloam_tile": (C.c_int, [_IP, _IP]),
     "slio_aloam_register_host": (C.c_int, [C.POINTER(SlioAloamParams), _FP, C.c_int64, _FP, _FP, _FP, _FP, _FP, _IP,
                                            _IP, _FP, _IP, _U8P, _IP, _IP]),
+    # include/slio_frontend.h (A-LOAM laserOdometry)
+    "slio_aloam_odom_params_default": (C.c_int, [C.POINTER(SlioAloamOdomParams)]),
+    "slio_aloam_odom_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioAloamOdomParams)]),
+    "slio_aloam_odom_destroy": (C.c_int, [_P]),
+    "slio_aloam_odom_reset": (C.c_int, [_P]),
+    "slio_aloam_odom_run": (C.c_int, [_P, _FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64,
+                                      C.POINTER(SlioAloamOdomResult)]),
+    "slio_aloam_odom_run_view": (C.c_int, [_P, C.POINTER(SlioAloamView), C.POINTER(SlioAloamOdomResult)]),
+    "slio_aloam_odom_get_last": (C.c_int, [_P, _FP, C.c_int64, _FP, C.c_int64, _IP]),
+    "slio_aloam_odom_get_view": (C.c_int, [_P, C.POINTER(SlioAloamOdomView)]),
+    "slio_aloam_odom_get_correspondences": (C.c_int, [_P, _IP, C.c_int64, _IP]),
+    "slio_aloam_odom_associate": (C.c_int, [_P, _DP, _DP]),
+    "slio_aloam_odom_evaluate": (C.c_int, [_P, _DP, _DP, _DP, _DP, _DP, _IP]),
+    "slio_aloam_odom_lm_step": (C.c_int, [C.POINTER(SlioAloamOdomLm), C.c_int, _DP, _DP, C.c_double]),
+    "slio_aloam_odom_host_associate": (C.c_int, [_FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64, _DP,
+                                                 _DP, _IP]),
+    "slio_aloam_odom_host_evaluate": (C.c_int, [_FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64, _IP,
+                                                _DP, _DP, _DP, _DP, _DP, _IP]),
+    "slio_aloam_odom_host_init": (C.c_int, [C.POINTER(SlioAloamOdomState)]),
+    "slio_aloam_odom_host_run": (C.c_int, [C.POINTER(SlioAloamOdomParams), C.POINTER(SlioAloamOdomState), _FP,
+                                           C.c_int64, _FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64,
+                                           C.POINTER(SlioAloamOdomResult)]),
 }
 
 _lib = None

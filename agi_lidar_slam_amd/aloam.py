@@ -9,9 +9,21 @@ cornerPointsLessSharp, surfPointsFlat, surfPointsLessFlat).  The clouds stay in
 HBM behind ``view()`` until the next run.  ``register_host`` is the host
 restatement (csrc/slio_aloam.cpp), callable without a GPU.  Input clouds are
 (n, 3) float32 in the message's order, output clouds (n, 4) float32 {x, y, z,
-intensity = scanID + scanPeriod * relTime}.  laserOdometry and laserMapping
-solve through Ceres and are not part of this package.  The stated departures
-are listed in slio_frontend.h and DESIGN.md §3.17.
+intensity = scanID + scanPeriod * relTime}.
+
+``AloamOdometry`` is the laserOdometry node's loop body
+(src/A-LOAM/src/laserOdometry.cpp:304-695) on the device, the slio_aloam_odom_*
+entries: the four feature clouds of a sweep in, /laser_odom_to_init out, from
+host clouds (``process``) or from a registration's device view
+(``process_view``).  ``AloamScanRegistration.enable_odometry`` puts one beside
+a registration, and ``laserOdometry(xyz)`` is then the sensor's cloud in and
+the pose out with only the raw cloud crossing PCIe.  ``AloamOdometryHost`` is
+the host restatement (csrc/slio_aloam_odom.cpp), callable without a GPU.  The
+association and the factors are the reference's; the solve is this library's
+own Levenberg-Marquardt in the shape of Ceres' trust-region defaults, and
+parity with Ceres' own iterates is unpinned.  laserMapping is not part of this
+package.  The stated departures are listed in slio_frontend.h and DESIGN.md
+§3.17 / §3.18.
 """
 from __future__ import annotations
 
@@ -77,7 +89,7 @@ class AloamScanRegistration:
     def __init__(self, n_scans: int = 16, minimum_range: float = 0.1, device: int = 0,
                  max_points: int = MAX_POINTS):
         self.lib = L.load()
-        self.n_scans = n_scans
+        self.n_scans, self.device, self.max_points = n_scans, device, max_points
         p = _params(n_scans, minimum_range, device, max_points)
         self.h = C.c_void_p()
         L.check(self.lib.slio_aloam_create(C.byref(self.h), C.byref(p)), "aloam_create")
@@ -144,3 +156,176 @@ class AloamScanRegistration:
         v = L.SlioAloamView()
         L.check(self.lib.slio_aloam_get_view(self.h, C.byref(v)), "aloam_get_view")
         return v
+
+    def enable_odometry(self, skip_frame_num: int = 2) -> "AloamOdometry":
+        """An AloamOdometry on this registration's device, fed by laserOdometry."""
+        self.odometry = AloamOdometry(self.n_scans, skip_frame_num, self.device, self.max_points)
+        return self.odometry
+
+    def laserOdometry(self, xyz) -> dict:
+        """scanRegistration's handler, then laserOdometry's loop body on its
+        clouds, device to device.  Returns the odometry's result."""
+        if getattr(self, "odometry", None) is None:
+            raise L.SlioError("laserOdometry: no enable_odometry before")
+        self.run(xyz)
+        return self.odometry.process_view(self.view())
+
+
+STOPS = ("max_iter", "gradient", "function", "parameter")
+PASS_FIELDS = ("corner", "plane", "degenerate", "iterations", "accepted", "outliers", "stop", "few", "cost_first",
+               "cost_last")
+
+
+def _xyzi(a) -> np.ndarray:
+    return np.ascontiguousarray(a, np.float32).reshape(-1, 4)
+
+
+def _odom_params(n_scans, skip_frame_num, device, max_points):
+    p = L.SlioAloamOdomParams()
+    L.check(L.load().slio_aloam_odom_params_default(C.byref(p)), "aloam_odom_params_default")
+    p.device, p.n_scans, p.max_points, p.skip_frame_num = device, n_scans, max_points, skip_frame_num
+    return p
+
+
+def _result(r: L.SlioAloamOdomResult) -> dict:
+    out = dict(q_w_curr=list(r.q_w_curr), t_w_curr=list(r.t_w_curr), q_last_curr=list(r.q_last_curr),
+               t_last_curr=list(r.t_last_curr), inited=r.inited, published=r.published, frame_count=r.frame_count,
+               passes=[])
+    for k in range(2 if r.inited else 0):
+        ps = r.passes[k]
+        d = {f: getattr(ps, f) for f in PASS_FIELDS}
+        d["iterates"] = [dict(q=list(ps.it_q[i]), t=list(ps.it_t[i]), cost=ps.it_cost[i], mu=ps.it_mu[i])
+                         for i in range(ps.iterations)]
+        out["passes"].append(d)
+    return out
+
+
+class AloamOdometry:
+    """laserOdometry's loop body (:304-695) on the device."""
+
+    def __init__(self, n_scans: int = 16, skip_frame_num: int = 2, device: int = 0, max_points: int = MAX_POINTS):
+        self.lib = L.load()
+        p = _odom_params(n_scans, skip_frame_num, device, max_points)
+        self.h = C.c_void_p()
+        L.check(self.lib.slio_aloam_odom_create(C.byref(self.h), C.byref(p)), "aloam_odom_create")
+        self.result = None
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self.lib.slio_aloam_odom_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def reset(self) -> None:
+        L.check(self.lib.slio_aloam_odom_reset(self.h), "aloam_odom_reset")
+        self.result = None
+
+    def process(self, sharp, less_sharp, flat, less_flat) -> dict:
+        """One sweep from cornerPointsSharp, cornerPointsLessSharp,
+        surfPointsFlat and surfPointsLessFlat on the host."""
+        a = [_xyzi(c) for c in (sharp, less_sharp, flat, less_flat)]
+        r = L.SlioAloamOdomResult()
+        args = [x for c in a for x in (L.fptr(c), c.shape[0])]
+        L.check(self.lib.slio_aloam_odom_run(self.h, *args, C.byref(r)), "aloam_odom_run")
+        self.result = _result(r)
+        return self.result
+
+    def process_view(self, view: L.SlioAloamView) -> dict:
+        """One sweep from a registration's device view."""
+        r = L.SlioAloamOdomResult()
+        L.check(self.lib.slio_aloam_odom_run_view(self.h, C.byref(view), C.byref(r)), "aloam_odom_run_view")
+        self.result = _result(r)
+        return self.result
+
+    @property
+    def pose(self):
+        """(q_w_curr (x, y, z, w), t_w_curr) after the last sweep."""
+        if self.result is None:
+            return [0.0, 0.0, 0.0, 1.0], [0.0, 0.0, 0.0]
+        return self.result["q_w_curr"], self.result["t_w_curr"]
+
+    def last_clouds(self):
+        """(laserCloudCornerLast, laserCloudSurfLast) on the host."""
+        n = np.zeros(2, np.int32)
+        L.check(self.lib.slio_aloam_odom_get_last(self.h, None, 0, None, 0, L.iptr(n)), "aloam_odom_get_last")
+        c, s = np.zeros((max(int(n[0]), 1), 4), np.float32), np.zeros((max(int(n[1]), 1), 4), np.float32)
+        L.check(self.lib.slio_aloam_odom_get_last(self.h, L.fptr(c), int(n[0]), L.fptr(s), int(n[1]), L.iptr(n)),
+                "aloam_odom_get_last")
+        return c[:n[0]], s[:n[1]]
+
+    def view(self) -> L.SlioAloamOdomView:
+        v = L.SlioAloamOdomView()
+        L.check(self.lib.slio_aloam_odom_get_view(self.h, C.byref(v)), "aloam_odom_get_view")
+        return v
+
+    # the lockstep entries, for tests
+    def associate(self, q, t) -> None:
+        q, t = np.ascontiguousarray(q, np.float64), np.ascontiguousarray(t, np.float64)
+        L.check(self.lib.slio_aloam_odom_associate(self.h, L.dptr(q), L.dptr(t)), "aloam_odom_associate")
+
+    def correspondences(self) -> np.ndarray:
+        corr, n = np.zeros((2304, 3), np.int32), np.zeros(1, np.int32)
+        L.check(self.lib.slio_aloam_odom_get_correspondences(self.h, L.iptr(corr), 2304, L.iptr(n)),
+                "aloam_odom_get_correspondences")
+        return corr[:n[0]]
+
+    def evaluate(self, q, t):
+        """(A[21], g[6], cost, counts {corner, plane, degenerate, outliers})."""
+        q, t = np.ascontiguousarray(q, np.float64), np.ascontiguousarray(t, np.float64)
+        A, g, cost, cnt = np.zeros(21), np.zeros(6), np.zeros(1), np.zeros(4, np.int32)
+        L.check(self.lib.slio_aloam_odom_evaluate(self.h, L.dptr(q), L.dptr(t), L.dptr(A), L.dptr(g), L.dptr(cost),
+                                                  L.iptr(cnt)), "aloam_odom_evaluate")
+        return A, g, float(cost[0]), [int(v) for v in cnt]
+
+
+def odom_host_associate(sharp, flat, corner_last, surf_last, q, t) -> np.ndarray:
+    a = [_xyzi(c) for c in (sharp, flat, corner_last, surf_last)]
+    q, t = np.ascontiguousarray(q, np.float64), np.ascontiguousarray(t, np.float64)
+    corr = np.zeros((a[0].shape[0] + a[1].shape[0] + 1, 3), np.int32)
+    args = [x for c in a for x in (L.fptr(c), c.shape[0])]
+    L.check(L.load().slio_aloam_odom_host_associate(*args, L.dptr(q), L.dptr(t), L.iptr(corr)),
+            "aloam_odom_host_associate")
+    return corr[:-1]
+
+
+def odom_host_evaluate(sharp, flat, corner_last, surf_last, corr, q, t):
+    a = [_xyzi(c) for c in (sharp, flat, corner_last, surf_last)]
+    q, t = np.ascontiguousarray(q, np.float64), np.ascontiguousarray(t, np.float64)
+    corr = np.ascontiguousarray(corr, np.int32)
+    A, g, cost, cnt = np.zeros(21), np.zeros(6), np.zeros(1), np.zeros(4, np.int32)
+    args = [x for c in a for x in (L.fptr(c), c.shape[0])]
+    L.check(L.load().slio_aloam_odom_host_evaluate(*args, L.iptr(corr), L.dptr(q), L.dptr(t), L.dptr(A), L.dptr(g),
+                                                   L.dptr(cost), L.iptr(cnt)), "aloam_odom_host_evaluate")
+    return A, g, float(cost[0]), [int(v) for v in cnt]
+
+
+class AloamOdometryHost:
+    """The same loop body on the host (slio_aloam_odom_host_run), no GPU."""
+
+    def __init__(self, n_scans: int = 16, skip_frame_num: int = 2, max_points: int = MAX_POINTS):
+        self.lib = L.load()
+        self.p = _odom_params(n_scans, skip_frame_num, 0, max_points)
+        self.st = L.SlioAloamOdomState()
+        self.reset()
+
+    def reset(self) -> None:
+        L.check(self.lib.slio_aloam_odom_host_init(C.byref(self.st)), "aloam_odom_host_init")
+        self.corner_last = self.surf_last = np.zeros((0, 4), np.float32)
+        self.result = None
+
+    def process(self, sharp, less_sharp, flat, less_flat) -> dict:
+        sharp, less_sharp, flat, less_flat = (_xyzi(c) for c in (sharp, less_sharp, flat, less_flat))
+        for c in (less_sharp, less_flat):           # what becomes a last cloud is checked on the way in
+            it = c[:, 3]
+            if not (np.all((it >= 0) & (it < 64)) and np.all(np.diff(it.astype(np.int64)) >= 0)):
+                raise L.SlioError("aloam_odom_host: EINVAL: scan ids of a less cloud decreasing or outside [0, 64)")
+        r = L.SlioAloamOdomResult()
+        a = (sharp, flat, self.corner_last, self.surf_last)
+        args = [x for c in a for x in (L.fptr(c), c.shape[0])]
+        L.check(self.lib.slio_aloam_odom_host_run(C.byref(self.p), C.byref(self.st), *args, C.byref(r)),
+                "aloam_odom_host_run")
+        self.corner_last, self.surf_last = less_sharp.copy(), less_flat.copy()
+        self.result = _result(r)
+        return self.result

@@ -505,6 +505,173 @@ int slio_aloam_register_host(const slio_aloam_params* p, const float* xyz, int64
                              float* surf_less_flat, int32_t* scan_start, int32_t* scan_end, float* curvature,
                              int32_t* label, uint8_t* picked, int32_t counts[5], int32_t* stats);
 
+/* ======================================================================
+ * A-LOAM laserOdometry (src/A-LOAM/src/laserOdometry.cpp; every path:line
+ * below is in that file unless said otherwise): the node's loop body :304-695
+ * on the device, from the four feature clouds of one sweep to
+ * /laser_odom_to_init.  DISTORTION is 0 as compiled (:52): s = 1, and
+ * Identity.slerp(1, q) rotates as q.  A sweep is
+ *   first sweep   :307-309  systemInited only
+ *   two passes    :317-593  each one association at the current para_q /
+ *                           para_t, then one solve:
+ *     TransformToStart :105-126  q * p + t in double, rounded to float
+ *     1-NN             :345, :457  exact, over the whole last cloud, gate < 25
+ *     second / third   :361-418, :476-539  the ring-bounded scans, as index
+ *                           ranges of the table ring_start[65]
+ *     factors          lidarFactor.hpp:12-125 with analytic Jacobians in the
+ *                           tangent [d theta (3), d t (3)], HuberLoss(0.1)
+ *     solve            :586-591  this library's own Levenberg-Marquardt in
+ *                           the shape of Ceres' trust-region defaults, at most
+ *                           4 iterations
+ *   integration   :600-601  t_w_curr += q_w_curr * t_last_curr, then q_w_curr
+ *                           *= q_last_curr, unnormalised
+ *   swap and gate :650-695  the two less clouds become the last clouds;
+ *                           published = (frameCount % skipFrameNum == 0)
+ * as at most six launches on the handle's stream and ONE host wait, for the
+ * result.  Quaternions are (x, y, z, w), as para_q (:55).
+ *
+ * Stated departures from the reference:
+ *  - the solve is not Ceres: parity with Ceres' own iterates is unpinned.
+ *    Every constant of the solve is in csrc/slio_aloam_odom.hpp; the
+ *    retraction is q' = normalize((d theta / 2, 1)) * q, so everything from
+ *    the association to the pose is + - * / sqrt in IEEE double and the
+ *    device, the host restatement and a numpy model agree to the bit;
+ *  - the 1-NN is exact with ties to the lower index (FLANN's order among
+ *    equal distances is unpinned);
+ *  - scan ids (int(intensity)) of the two less clouds must be non-decreasing
+ *    in the index and inside [0, 64): EINVAL otherwise, with no change of the
+ *    handle's state.  It holds for the clouds of slio_aloam_*;
+ *  - an empty last cloud gives no factor (the reference reads a stale
+ *    pointSearchSqDis[0]);
+ *  - a factor with coincident edge points or a non-finite plane normal is
+ *    dropped and counted as degenerate (the reference divides by zero);
+ *  - the sums run over factor slots in query order (sharp, then flat), 32
+ *    strided partials per entry in ascending slot, then ascending lane;
+ *  - the `if (0)` block (:630-648), the publishers and the path message are
+ *    not restated.
+ * ====================================================================== */
+typedef struct slio_aloam_odom* slio_aloam_odom_handle;
+
+typedef struct slio_aloam_odom_params {
+  int32_t device;
+  int32_t n_scans;        /* 1 .. 64: sharp <= 12 n_scans, flat <= 24 n_scans queries per sweep */
+  int32_t max_points;     /* capacity of each less cloud, 1 .. 400000 */
+  int32_t skip_frame_num; /* mapping_skip_frame (:199), >= 1; default 2, 1 in the launch files */
+  int32_t reserved[4];
+} slio_aloam_odom_params;
+
+/* One opti pass (:317). stop: 0 max_num_iterations, 1 gradient, 2 function,
+ * 3 parameter.  it_*[k]: the point, its cost and the radius mu after
+ * iteration k (k < iterations).  few: corner + plane < 10 (:579). */
+typedef struct slio_aloam_odom_pass {
+  int32_t corner, plane, degenerate, iterations, accepted, outliers, stop, few;
+  double cost_first, cost_last;
+  double it_q[4][4], it_t[4][3], it_cost[4], it_mu[4];
+} slio_aloam_odom_pass;
+
+typedef struct slio_aloam_odom_result {
+  double q_w_curr[4], t_w_curr[3];       /* /laser_odom_to_init (:607-619) */
+  double q_last_curr[4], t_last_curr[3]; /* para_q, para_t */
+  int32_t inited;    /* systemInited was set before this sweep: the passes ran */
+  int32_t published; /* the skipFrameNum gate (:667) opened */
+  int32_t frame_count, reserved;
+  slio_aloam_odom_pass pass[2];
+} slio_aloam_odom_result;
+
+/* The host-side state of slio_aloam_odom_host_run: what the node keeps
+ * between sweeps besides the last clouds. */
+typedef struct slio_aloam_odom_state {
+  double q_w_curr[4], t_w_curr[3], para_q[4], para_t[3];
+  int32_t inited, frame_count;
+} slio_aloam_odom_state;
+
+/* The controller's state of one solve (slio_aloam_odom_lm_step). */
+typedef struct slio_aloam_odom_lm {
+  double mu, nu;
+  double q[4], t[3];
+  double A[21], g[6], cost;
+  double delta[6], model, xnorm;
+  double qn[4], tn[3];
+  int32_t pivots_ok, iterations, accepted, stop, done, last_accepted;
+} slio_aloam_odom_lm;
+
+/* The last clouds on the device: n x {x, y, z, intensity}, valid until the
+ * next run. */
+typedef struct slio_aloam_odom_view {
+  const float* corner_last;
+  const float* surf_last;
+  int32_t n_corner, n_surf, device, reserved;
+} slio_aloam_odom_view;
+
+/* device 0, n_scans 16, max_points 400000, skip_frame_num 2. */
+int slio_aloam_odom_params_default(slio_aloam_odom_params* p);
+/* EINVAL: n_scans outside 1 .. 64, max_points outside 1 .. 400000,
+ * skip_frame_num < 1, negative device (before any device call), no such
+ * device. */
+int slio_aloam_odom_create(slio_aloam_odom_handle* out, const slio_aloam_odom_params* p);
+int slio_aloam_odom_destroy(slio_aloam_odom_handle h);
+/* Back to the state after create: identity poses, systemInited false,
+ * frameCount 0 (:42-50, :55-59). */
+int slio_aloam_odom_reset(slio_aloam_odom_handle h);
+/* One sweep (:304-695) from four host clouds, n x {x, y, z, intensity} each.
+ * EINVAL: a negative size, a null cloud with a size > 0, a null result, scan
+ * ids of a less cloud decreasing or outside [0, 64); ECAPACITY: more sharp
+ * points than 12 n_scans, flat than 24 n_scans, or less points than
+ * max_points.  Returns after the handle's stream has finished. */
+int slio_aloam_odom_run(slio_aloam_odom_handle h, const float* sharp, int64_t n_sharp, const float* less_sharp,
+                        int64_t n_less_sharp, const float* flat, int64_t n_flat, const float* less_flat,
+                        int64_t n_less_flat, slio_aloam_odom_result* res);
+/* The same from the device-resident clouds of slio_aloam_get_view (which has
+ * waited for the registration's stream); the clouds are copied device to
+ * device, so the view may be overwritten afterwards.  EINVAL also for a view
+ * of another device; the ids are checked by the kernel that copies. */
+int slio_aloam_odom_run_view(slio_aloam_odom_handle h, const slio_aloam_view* v, slio_aloam_odom_result* res);
+/* laserCloudCornerLast / laserCloudSurfLast (:650-659) to the host.  counts =
+ * {corner, surf}.  ESTATE before a sweep; ECAPACITY where a cap is short. */
+int slio_aloam_odom_get_last(slio_aloam_odom_handle h, float* corner_last, int64_t cap_corner, float* surf_last,
+                             int64_t cap_surf, int32_t counts[2]);
+int slio_aloam_odom_get_view(slio_aloam_odom_handle h, slio_aloam_odom_view* v);
+/* (closest, second, third) per factor slot of the last association: the
+ * sharp queries, then the flat ones; -1: none (a corner has no third).  n =
+ * the slots.  ESTATE before an association; ECAPACITY: cap_slots < n. */
+int slio_aloam_odom_get_correspondences(slio_aloam_odom_handle h, int32_t* corr, int64_t cap_slots, int32_t* n);
+/* -- lockstep entries, for tests -- */
+/* One association (:341-573) of the last sweep's sharp and flat points at
+ * (q, t) against the last clouds, which after a first sweep are that sweep's
+ * own less clouds.  ESTATE before a sweep. */
+int slio_aloam_odom_associate(slio_aloam_odom_handle h, const double q[4], const double t[3]);
+/* The factors of the last association at (q, t): A = sum w J^T J (upper
+ * triangle, row-major), g = sum w J^T r, cost = 1/2 sum rho, counts =
+ * {corner, plane, degenerate, outliers}.  ESTATE before an association. */
+int slio_aloam_odom_evaluate(slio_aloam_odom_handle h, const double q[4], const double t[3], double A[21],
+                             double g[6], double* cost, int32_t counts[4]);
+/* -- host only, callable without a GPU -- */
+/* The controller.  phase 0: start a solve at (lm->q, lm->t) with the
+ * evaluation (lm->A, lm->g, lm->cost) there: mu 1e4, nu 2.  phase 1: the first
+ * half of an iteration: the gradient stop, the damped LDL^T solve, the model
+ * decrease, the proposed point (qn, tn); returns with lm->done set where the
+ * solve has stopped.  phase 2: the second half, with the evaluation (A, g,
+ * cost) at the proposed point: accept or reject, the radius, the function and
+ * parameter stops. */
+int slio_aloam_odom_lm_step(slio_aloam_odom_lm* lm, int phase, const double A[21], const double g[6], double cost);
+/* The association as its literal serial loops.  corr: 3 ints per slot. */
+int slio_aloam_odom_host_associate(const float* sharp, int64_t n_sharp, const float* flat, int64_t n_flat,
+                                   const float* corner_last, int64_t n_corner, const float* surf_last,
+                                   int64_t n_surf, const double q[4], const double t[3], int32_t* corr);
+int slio_aloam_odom_host_evaluate(const float* sharp, int64_t n_sharp, const float* flat, int64_t n_flat,
+                                  const float* corner_last, int64_t n_corner, const float* surf_last,
+                                  int64_t n_surf, const int32_t* corr, const double q[4], const double t[3],
+                                  double A[21], double g[6], double* cost, int32_t counts[4]);
+/* state to identity poses, not inited, frame_count 0. */
+int slio_aloam_odom_host_init(slio_aloam_odom_state* st);
+/* One sweep on the host: the passes against (corner_last, surf_last), the
+ * integration and the gate; the caller then makes its less clouds the last
+ * ones.  p->device is not read. */
+int slio_aloam_odom_host_run(const slio_aloam_odom_params* p, slio_aloam_odom_state* st, const float* sharp,
+                             int64_t n_sharp, const float* flat, int64_t n_flat, const float* corner_last,
+                             int64_t n_corner, const float* surf_last, int64_t n_surf,
+                             slio_aloam_odom_result* res);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,11 @@
   aloam_reg A-LOAM's scanRegistration (AloamScanRegistration: slio_aloam_*) on a VLP-16
             sweep (horizon 1800) and a 64-line sweep (horizon 2083): ms per registration,
             the five counts, the host restatement beside it (only when named)
+  aloam_odom A-LOAM's laserOdometry (AloamOdometry: slio_aloam_odom_*) on the same two inputs
+            as two consecutive sweeps of a moving sensor: ms per odometry call and its split
+            into association and solve, correspondences, iterations, launches and waits,
+            registration plus odometry per sweep, the host restatement beside it (only
+            when named)
   livox_reg livox_mapping's scanRegistration (LivoxScanRegistration: slio_lreg_*) on a
             dense continuous-curve frame of about 24,000 returns: ms per registration,
             the counts, the host restatement beside it; then process_cloud (sensor's
@@ -882,8 +887,76 @@ def aloam_reg(reps=20):
                       "host_waits_per_registration": 1, "kernel_times": "not measured"}), flush=True)
 
 
+def aloam_odom(reps=20):
+    """A-LOAM's laserOdometry (AloamOdometry: slio_aloam_odom_*) on aloam_reg's
+    two inputs.  The second sweep is the first one's returns seen from a
+    sensor that has moved by 0.02 rad of yaw and (0.15, 0.04, 0) m; the two
+    alternate, so every call is a full odometry call (two associations, two
+    solves) between different sweeps.  Host wall clock around synchronous
+    calls, mean of `reps` after a warm-up: ms per odometry call from host
+    feature clouds; ms of one association launch and its wait (the lockstep
+    entry), from which the split is estimated as 2 associations + the rest; ms
+    per sweep of registration plus odometry, device to device; the same calls
+    through the host restatement (one thread) beside it."""
+    from agi_lidar_slam_amd import synth
+    from agi_lidar_slam_amd.aloam import (CLOUDS, AloamOdometry, AloamOdometryHost, AloamScanRegistration,
+                                          register_host)
+    upper, lower = 2.0 - np.arange(33) / 3.0, -8.83 - np.arange(1, 32) / 2.0
+    inputs = (("vlp16_h1800", 16, -15.0 + 2.0 * np.arange(16), 1800),
+              ("hdl64_h2083", 64, np.concatenate([upper, lower]), 2083))
+    rows = []
+    for name, n_scans, beams, horizon in inputs:
+        sw = synth.make_spinning_sweep(beams, horizon=horizon)
+        a = np.ascontiguousarray(np.stack([sw["x"], sw["y"], sw["z"]], 1), np.float32)
+        c, s_ = np.cos(0.02), np.sin(0.02)
+        d = a.astype(np.float64) - np.array([0.15, 0.04, 0.0])
+        b = np.ascontiguousarray(np.stack([c * d[:, 0] + s_ * d[:, 1], -s_ * d[:, 0] + c * d[:, 1], d[:, 2]], 1),
+                                 np.float32)
+        raw = (a, b)
+        feats = [tuple(register_host(x, n_scans=n_scans)[k] for k in CLOUDS[1:]) for x in raw]
+        od = AloamOdometry(n_scans=n_scans, skip_frame_num=1)
+        host = AloamOdometryHost(n_scans=n_scans, skip_frame_num=1)
+        for k in range(3):                               # warm-up; both now hold sweep 0 as the last clouds
+            r_dev, r_host = od.process(*feats[k % 2]), host.process(*feats[k % 2])
+        same = r_dev == r_host
+        t0, k0 = time.perf_counter(), 3
+        for k in range(k0, k0 + reps):
+            r_dev = od.process(*feats[k % 2])
+        ms_odom = (time.perf_counter() - t0) * 1e3 / reps
+        t0 = time.perf_counter()
+        for k in range(k0, k0 + 4):
+            r_host = host.process(*feats[k % 2])
+        ms_host = (time.perf_counter() - t0) * 1e3 / 4
+        ms_assoc, _ = t_ms(lambda: od.associate(r_dev["q_last_curr"], r_dev["t_last_curr"]), reps)
+        reg = AloamScanRegistration(n_scans=n_scans)
+        reg.enable_odometry(skip_frame_num=1)
+        for k in range(3):
+            reg.laserOdometry(raw[k % 2])
+        t0 = time.perf_counter()
+        for k in range(3, 3 + reps):
+            r_view = reg.laserOdometry(raw[k % 2])
+        ms_sweep = (time.perf_counter() - t0) * 1e3 / reps
+        ps = r_dev["passes"]
+        rows.append({"input": name, "points": int(len(a)), "queries": [int(len(feats[1][0])), int(len(feats[1][2]))],
+                     "last_points": [int(len(feats[0][1])), int(len(feats[0][3]))],
+                     "ms_per_odometry_call": ms_odom, "ms_one_association_and_wait": ms_assoc,
+                     "ms_two_solves_and_rest_est": ms_odom - 2 * ms_assoc,
+                     "correspondences": [[p["corner"], p["plane"]] for p in ps],
+                     "iterations": [p["iterations"] for p in ps], "stops": [p["stop"] for p in ps],
+                     "ms_registration_plus_odometry": ms_sweep,
+                     "view_pose_same_bits_as_host_clouds": bool(r_view["q_last_curr"] == r_dev["q_last_curr"]),
+                     "ms_host_restatement": ms_host, "host_same_bits_as_device": bool(same)})
+        for h in (od, reg.odometry, reg):
+            h.close()
+    print(json.dumps({"bench": "aloam_odom", "inputs": rows,
+                      "launches_per_odometry_call": "1 memset + 5 kernels (store_last, 2 x assoc, 2 x solve)",
+                      "host_waits_per_odometry_call": 1, "kernel_times": "not measured"}), flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "aloam_odom" in what:
+        aloam_odom()
     if "aloam_reg" in what:
         aloam_reg()
     if "livox_reg" in what:
