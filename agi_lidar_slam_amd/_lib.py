@@ -278,6 +278,20 @@ class SlioAloamOdomView(C.Structure):
                 ("n_surf", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SlioAloamMapParams(C.Structure):
+    """slio_aloam_map_params (include/slio_frontend.h)."""
+    _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("max_scan", C.c_int32),
+                ("leaf_corner", C.c_float), ("leaf_surf", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class SlioAloamMapResult(C.Structure):
+    """slio_aloam_map_result (include/slio_frontend.h)."""
+    _fields_ = [("q_w_curr", C.c_double * 4), ("t_w_curr", C.c_double * 3), ("q_wmap_wodom", C.c_double * 4),
+                ("t_wmap_wodom", C.c_double * 3), ("center", C.c_int32 * 3), ("shift", C.c_int32 * 3),
+                ("map_size", C.c_int32 * 2), ("stack_size", C.c_int32 * 2), ("optimized", C.c_int32),
+                ("nvalid", C.c_int32), ("passes", SlioAloamOdomPass * 2)]
+
+
 class SlioLmapParams(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("leaf_corner", C.c_float),
                 ("leaf_surf", C.c_float), ("leaf_outlier", C.c_float), ("pose_leaf", C.c_float),
@@ -513,6 +527,34 @@ SIGNATURES = {
     "slio_aloam_odom_host_run": (C.c_int, [C.POINTER(SlioAloamOdomParams), C.POINTER(SlioAloamOdomState), _FP,
                                            C.c_int64, _FP, C.c_int64, _FP, C.c_int64, _FP, C.c_int64,
                                            C.POINTER(SlioAloamOdomResult)]),
+    "slio_aloam_map_params_default": (C.c_int, [C.POINTER(SlioAloamMapParams)]),
+    "slio_aloam_map_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioAloamMapParams)]),
+    "slio_aloam_map_destroy": (C.c_int, [_P]),
+    "slio_aloam_map_reset": (C.c_int, [_P]),
+    "slio_aloam_map_run": (C.c_int, [_P, _FP, C.c_int64, _FP, C.c_int64, _DP, _DP, C.POINTER(SlioAloamMapResult)]),
+    "slio_aloam_map_run_view": (C.c_int, [_P, C.POINTER(SlioAloamOdomView), _DP, _DP,
+                                          C.POINTER(SlioAloamMapResult)]),
+    "slio_aloam_map_register_cloud": (C.c_int, [_P, C.c_void_p, C.c_int64, C.c_int, _FP]),
+    "slio_aloam_map_get_cube": (C.c_int, [_P, C.c_int, C.c_int32, _FP, C.c_int64, _I64P]),
+    "slio_aloam_map_cube_sizes": (C.c_int, [_P, C.c_int, _IP]),
+    "slio_aloam_map_get_surround": (C.c_int, [_P, C.c_int, _FP, C.c_int64, _I64P]),
+    "slio_aloam_map_get_map": (C.c_int, [_P, C.c_int, _FP, C.c_int64, _I64P]),
+    "slio_aloam_map_get_stack": (C.c_int, [_P, C.c_int, _FP, C.c_int64, _I64P]),
+    "slio_aloam_map_associate": (C.c_int, [_P, _DP, _DP]),
+    "slio_aloam_map_get_association": (C.c_int, [_P, _U8P, _DP, _IP, _FP, C.c_int64, _IP]),
+    "slio_aloam_map_evaluate": (C.c_int, [_P, _DP, _DP, _DP, _DP, _DP, _IP]),
+    "slio_aloam_map_predict": (C.c_int, [_DP, _DP, _DP, _DP, _DP, _DP]),
+    "slio_aloam_map_host_select": (C.c_int, [_DP, _IP, _IP, _IP, _IP, _IP]),
+    "slio_aloam_map_host_fit_line": (C.c_int, [_DP, _DP, _DP, _DP, _DP]),
+    "slio_aloam_map_host_fit_plane": (C.c_int, [_DP, _DP, _DP, _DP]),
+    "slio_aloam_map_host_evaluate": (C.c_int, [_FP, _U8P, _DP, C.c_int64, _DP, _DP, _DP, _DP, _DP, _IP]),
+    "slio_aloam_map_host_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioAloamMapParams)]),
+    "slio_aloam_map_host_destroy": (C.c_int, [_P]),
+    "slio_aloam_map_host_run": (C.c_int, [_P, _FP, C.c_int64, _FP, C.c_int64, _DP, _DP,
+                                          C.POINTER(SlioAloamMapResult)]),
+    "slio_aloam_map_host_get_cube": (C.c_int, [_P, C.c_int, C.c_int32, _FP, C.c_int64, _I64P]),
+    "slio_aloam_map_host_get_stack": (C.c_int, [_P, C.c_int, _FP, C.c_int64, _I64P]),
+    "slio_aloam_map_host_get_association": (C.c_int, [_P, _U8P, _DP, _IP, _FP, C.c_int64, _IP]),
 }
 
 _lib = None

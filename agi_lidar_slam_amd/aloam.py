@@ -21,9 +21,17 @@ the pose out with only the raw cloud crossing PCIe.  ``AloamOdometryHost`` is
 the host restatement (csrc/slio_aloam_odom.cpp), callable without a GPU.  The
 association and the factors are the reference's; the solve is this library's
 own Levenberg-Marquardt in the shape of Ceres' trust-region defaults, and
-parity with Ceres' own iterates is unpinned.  laserMapping is not part of this
-package.  The stated departures are listed in slio_frontend.h and DESIGN.md
-§3.17 / §3.18.
+parity with Ceres' own iterates is unpinned.
+
+``AloamMapping`` is the laserMapping node's loop body
+(src/A-LOAM/src/laserMapping.cpp:326-893) on the device, the slio_aloam_map_*
+entries: the odometry's two last clouds and its pose in, /aft_mapped_to_init
+out, with the rolling 21 x 21 x 11 cube map in HBM.
+``AloamScanRegistration.enable_mapping`` puts an odometry and a mapper beside a
+registration, and ``laserMapping(xyz)`` is then the whole chain with only the
+raw cloud crossing PCIe.  ``AloamMappingHost`` is the host restatement
+(csrc/slio_aloam_map.cpp).  The stated departures are listed in slio_frontend.h
+and DESIGN.md §3.17 - §3.19.
 """
 from __future__ import annotations
 
@@ -169,6 +177,29 @@ class AloamScanRegistration:
             raise L.SlioError("laserOdometry: no enable_odometry before")
         self.run(xyz)
         return self.odometry.process_view(self.view())
+
+    def enable_mapping(self, skip_frame_num: int = 2, leaf_corner: float = 0.4, leaf_surf: float = 0.8,
+                       max_map_points: int = 1 << 21) -> "AloamMapping":
+        """An AloamOdometry (unless enable_odometry made one) and an
+        AloamMapping on this registration's device, fed by laserMapping."""
+        if getattr(self, "odometry", None) is None:
+            self.enable_odometry(skip_frame_num)
+        self.mapping = AloamMapping(leaf_corner, leaf_surf, self.device, max_map_points, self.max_points)
+        return self.mapping
+
+    def laserMapping(self, xyz) -> dict:
+        """The three nodes on one sweep: scanRegistration's handler,
+        laserOdometry's loop body and, on the sweeps the odometry publishes
+        (laserOdometry.cpp:667), laserMapping's loop body on the odometry's
+        last clouds, all device to device.  Returns dict(odometry=..,
+        mapping=.. or None where the gate stayed shut)."""
+        if getattr(self, "mapping", None) is None:
+            raise L.SlioError("laserMapping: no enable_mapping before")
+        od = self.laserOdometry(xyz)
+        mp = None
+        if od["published"]:
+            mp = self.mapping.process_view(self.odometry.view(), od["q_w_curr"], od["t_w_curr"])
+        return dict(odometry=od, mapping=mp)
 
 
 STOPS = ("max_iter", "gradient", "function", "parameter")
@@ -329,3 +360,246 @@ class AloamOdometryHost:
         self.corner_last, self.surf_last = less_sharp.copy(), less_flat.copy()
         self.result = _result(r)
         return self.result
+
+
+# ---------------------------------------------------------------- laserMapping
+KINDS = ("none", "edge", "plane", "degenerate", "rejected")
+N_CUBES = 21 * 21 * 11
+
+
+def _map_params(leaf_corner, leaf_surf, device, max_points, max_scan):
+    p = L.SlioAloamMapParams()
+    L.check(L.load().slio_aloam_map_params_default(C.byref(p)), "aloam_map_params_default")
+    p.device, p.max_points, p.max_scan = device, max_points, max_scan
+    p.leaf_corner, p.leaf_surf = leaf_corner, leaf_surf
+    return p
+
+
+def _pose(q, t):
+    return np.ascontiguousarray(q, np.float64).reshape(4), np.ascontiguousarray(t, np.float64).reshape(3)
+
+
+def _map_result(r: L.SlioAloamMapResult) -> dict:
+    out = dict(q_w_curr=list(r.q_w_curr), t_w_curr=list(r.t_w_curr), q_wmap_wodom=list(r.q_wmap_wodom),
+               t_wmap_wodom=list(r.t_wmap_wodom), center=list(r.center), shift=list(r.shift),
+               map_size=list(r.map_size), stack_size=list(r.stack_size), optimized=r.optimized, nvalid=r.nvalid,
+               passes=[])
+    for k in range(2 if r.optimized else 0):
+        ps = r.passes[k]
+        d = {f: getattr(ps, f) for f in PASS_FIELDS}
+        d["iterates"] = [dict(q=list(ps.it_q[i]), t=list(ps.it_t[i]), cost=ps.it_cost[i], mu=ps.it_mu[i])
+                         for i in range(ps.iterations)]
+        out["passes"].append(d)
+    return out
+
+
+def map_predict(q_wmap_wodom, t_wmap_wodom, q_wodom_curr, t_wodom_curr):
+    """The high-frequency pose (laserMapping.cpp:222-223)."""
+    a, b = _pose(q_wmap_wodom, t_wmap_wodom)
+    c, d = _pose(q_wodom_curr, t_wodom_curr)
+    q, t = np.zeros(4), np.zeros(3)
+    L.check(L.load().slio_aloam_map_predict(L.dptr(a), L.dptr(b), L.dptr(c), L.dptr(d), L.dptr(q), L.dptr(t)),
+            "aloam_map_predict")
+    return list(q), list(t)
+
+
+def map_host_select(t_w_curr, cen):
+    """(centre cube, shift, cube list); cen (3 ints) is updated in place."""
+    t = np.ascontiguousarray(t_w_curr, np.float64).reshape(3)
+    c = np.array(cen, np.int32)
+    center, shift, lst, n = np.zeros(3, np.int32), np.zeros(3, np.int32), np.zeros(75, np.int32), np.zeros(1, np.int32)
+    L.check(L.load().slio_aloam_map_host_select(L.dptr(t), L.iptr(c), L.iptr(center), L.iptr(shift), L.iptr(lst),
+                                                L.iptr(n)), "aloam_map_host_select")
+    cen[:] = [int(v) for v in c]
+    return [int(v) for v in center], [int(v) for v in shift], [int(v) for v in lst[:n[0]]]
+
+
+def map_host_fit_line(nb):
+    """(kind, a, b, eigenvalues, eigenvectors in columns) of five neighbours."""
+    nb = np.ascontiguousarray(nb, np.float64).reshape(5, 3)
+    a, b, lam, vec = np.zeros(3), np.zeros(3), np.zeros(3), np.zeros((3, 3))
+    k = L.load().slio_aloam_map_host_fit_line(L.dptr(nb), L.dptr(a), L.dptr(b), L.dptr(lam), L.dptr(vec))
+    if k < 0:
+        L.check(k, "aloam_map_host_fit_line")
+    return k, a, b, lam, vec
+
+
+def map_host_fit_plane(nb):
+    """(kind, unit normal, d, the solution x of A x = -1) of five neighbours."""
+    nb = np.ascontiguousarray(nb, np.float64).reshape(5, 3)
+    n, d, x = np.zeros(3), np.zeros(1), np.zeros(3)
+    k = L.load().slio_aloam_map_host_fit_plane(L.dptr(nb), L.dptr(n), L.dptr(d), L.dptr(x))
+    if k < 0:
+        L.check(k, "aloam_map_host_fit_plane")
+    return k, n, float(d[0]), x
+
+
+def map_host_evaluate(xyz, kind, rec, q, t):
+    """(A[21], g[6], cost, counts {edge, plane, degenerate, outliers}) over the slots."""
+    xyz = _xyz(xyz)
+    kind = np.ascontiguousarray(kind, np.uint8)
+    rec = np.ascontiguousarray(rec, np.float64).reshape(-1, 6)
+    q, t = _pose(q, t)
+    A, g, cost, cnt = np.zeros(21), np.zeros(6), np.zeros(1), np.zeros(4, np.int32)
+    L.check(L.load().slio_aloam_map_host_evaluate(L.fptr(xyz), L.u8ptr(kind), L.dptr(rec), xyz.shape[0], L.dptr(q),
+                                                  L.dptr(t), L.dptr(A), L.dptr(g), L.dptr(cost), L.iptr(cnt)),
+            "aloam_map_host_evaluate")
+    return A, g, float(cost[0]), [int(v) for v in cnt]
+
+
+class _MapCommon:
+    """What AloamMapping and AloamMappingHost share: the getters by entry name."""
+
+    def _cloud(self, fn, what, *args) -> np.ndarray:
+        n = C.c_int64()
+        L.check(fn(self.h, *args, None, 0, C.byref(n)), what)
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        L.check(fn(self.h, *args, L.fptr(out), n.value, C.byref(n)), what)
+        return out[:n.value]
+
+    def _association(self, fn, what):
+        n = np.zeros(1, np.int32)
+        rc = fn(self.h, None, None, None, None, 0, L.iptr(n))
+        if rc not in (0, -4):
+            L.check(rc, what)
+        m = max(int(n[0]), 1)
+        kind, rec = np.zeros(m, np.uint8), np.zeros((m, 6))
+        idx, sqd = np.zeros((m, 5), np.int32), np.zeros((m, 5), np.float32)
+        L.check(fn(self.h, L.u8ptr(kind), L.dptr(rec), L.iptr(idx), L.fptr(sqd), m, L.iptr(n)), what)
+        k = int(n[0])
+        return kind[:k], rec[:k], idx[:k], sqd[:k]
+
+
+class AloamMapping(_MapCommon):
+    """laserMapping's loop body (:326-893) on the device."""
+
+    def __init__(self, leaf_corner: float = 0.4, leaf_surf: float = 0.8, device: int = 0,
+                 max_points: int = 1 << 21, max_scan: int = MAX_POINTS):
+        self.lib = L.load()
+        p = _map_params(leaf_corner, leaf_surf, device, max_points, max_scan)
+        self.h = C.c_void_p()
+        L.check(self.lib.slio_aloam_map_create(C.byref(self.h), C.byref(p)), "aloam_map_create")
+        self.result = None
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self.lib.slio_aloam_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def reset(self) -> None:
+        L.check(self.lib.slio_aloam_map_reset(self.h), "aloam_map_reset")
+        self.result = None
+
+    def process(self, corner_last, surf_last, q_wodom_curr, t_wodom_curr) -> dict:
+        """One sweep from laserCloudCornerLast / laserCloudSurfLast on the host
+        ((n, 4) float32) and /laser_odom_to_init."""
+        c, s = _xyzi(corner_last), _xyzi(surf_last)
+        q, t = _pose(q_wodom_curr, t_wodom_curr)
+        r = L.SlioAloamMapResult()
+        L.check(self.lib.slio_aloam_map_run(self.h, L.fptr(c), c.shape[0], L.fptr(s), s.shape[0], L.dptr(q), L.dptr(t),
+                                            C.byref(r)), "aloam_map_run")
+        self.result = _map_result(r)
+        return self.result
+
+    def process_view(self, view: L.SlioAloamOdomView, q_wodom_curr, t_wodom_curr) -> dict:
+        """One sweep from an odometry's device view."""
+        q, t = _pose(q_wodom_curr, t_wodom_curr)
+        r = L.SlioAloamMapResult()
+        L.check(self.lib.slio_aloam_map_run_view(self.h, C.byref(view), L.dptr(q), L.dptr(t), C.byref(r)),
+                "aloam_map_run_view")
+        self.result = _map_result(r)
+        return self.result
+
+    def register_cloud(self, xyzi) -> np.ndarray:
+        """laserCloudFullRes in the map frame (:929-933), from the host."""
+        c = _xyzi(xyzi)
+        out = np.zeros((max(c.shape[0], 1), 4), np.float32)
+        L.check(self.lib.slio_aloam_map_register_cloud(self.h, c.ctypes.data_as(C.c_void_p), c.shape[0], 0,
+                                                       L.fptr(out)), "aloam_map_register_cloud")
+        return out[:c.shape[0]]
+
+    def register_device_cloud(self, ptr, n: int) -> np.ndarray:
+        """The same from a device cloud (a registration's view)."""
+        out = np.zeros((max(n, 1), 4), np.float32)
+        L.check(self.lib.slio_aloam_map_register_cloud(self.h, C.c_void_p(ptr), n, 1, L.fptr(out)),
+                "aloam_map_register_cloud")
+        return out[:n]
+
+    def cube(self, kind: int, ind: int) -> np.ndarray:
+        return self._cloud(self.lib.slio_aloam_map_get_cube, "aloam_map_get_cube", kind, ind)
+
+    def cube_sizes(self, kind: int) -> np.ndarray:
+        out = np.zeros(N_CUBES, np.int32)
+        L.check(self.lib.slio_aloam_map_cube_sizes(self.h, kind, L.iptr(out)), "aloam_map_cube_sizes")
+        return out
+
+    def surround(self, kind: int) -> np.ndarray:
+        return self._cloud(self.lib.slio_aloam_map_get_surround, "aloam_map_get_surround", kind)
+
+    def map(self, kind: int) -> np.ndarray:
+        return self._cloud(self.lib.slio_aloam_map_get_map, "aloam_map_get_map", kind)
+
+    def stack(self, kind: int) -> np.ndarray:
+        return self._cloud(self.lib.slio_aloam_map_get_stack, "aloam_map_get_stack", kind)
+
+    # the lockstep entries, for tests
+    def associate(self, q, t) -> None:
+        q, t = _pose(q, t)
+        L.check(self.lib.slio_aloam_map_associate(self.h, L.dptr(q), L.dptr(t)), "aloam_map_associate")
+
+    def association(self):
+        """(kind, record, neighbour indices, squared distances) per slot."""
+        return self._association(self.lib.slio_aloam_map_get_association, "aloam_map_get_association")
+
+    def evaluate(self, q, t):
+        q, t = _pose(q, t)
+        A, g, cost, cnt = np.zeros(21), np.zeros(6), np.zeros(1), np.zeros(4, np.int32)
+        L.check(self.lib.slio_aloam_map_evaluate(self.h, L.dptr(q), L.dptr(t), L.dptr(A), L.dptr(g), L.dptr(cost),
+                                                 L.iptr(cnt)), "aloam_map_evaluate")
+        return A, g, float(cost[0]), [int(v) for v in cnt]
+
+
+class AloamMappingHost(_MapCommon):
+    """The same loop body on the host (slio_aloam_map_host_run), no GPU."""
+
+    def __init__(self, leaf_corner: float = 0.4, leaf_surf: float = 0.8, max_points: int = 1 << 21,
+                 max_scan: int = MAX_POINTS):
+        self.lib = L.load()
+        self.p = _map_params(leaf_corner, leaf_surf, 0, max_points, max_scan)
+        self.h = C.c_void_p()
+        self.reset()
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self.lib.slio_aloam_map_host_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def reset(self) -> None:
+        self.close()
+        self.h = C.c_void_p()
+        L.check(self.lib.slio_aloam_map_host_create(C.byref(self.h), C.byref(self.p)), "aloam_map_host_create")
+        self.result = None
+
+    def process(self, corner_last, surf_last, q_wodom_curr, t_wodom_curr) -> dict:
+        c, s = _xyzi(corner_last), _xyzi(surf_last)
+        q, t = _pose(q_wodom_curr, t_wodom_curr)
+        r = L.SlioAloamMapResult()
+        L.check(self.lib.slio_aloam_map_host_run(self.h, L.fptr(c), c.shape[0], L.fptr(s), s.shape[0], L.dptr(q),
+                                                 L.dptr(t), C.byref(r)), "aloam_map_host_run")
+        self.result = _map_result(r)
+        return self.result
+
+    def cube(self, kind: int, ind: int) -> np.ndarray:
+        return self._cloud(self.lib.slio_aloam_map_host_get_cube, "aloam_map_host_get_cube", kind, ind)
+
+    def stack(self, kind: int) -> np.ndarray:
+        return self._cloud(self.lib.slio_aloam_map_host_get_stack, "aloam_map_host_get_stack", kind)
+
+    def association(self):
+        return self._association(self.lib.slio_aloam_map_host_get_association, "aloam_map_host_get_association")

@@ -22,6 +22,11 @@
 //                            per point of any other cube
 //   offsets   k_lvx_offsets  the new table; read back (19 KB) with the total
 //
+// Everything from "shift" to "offsets", the gather of listed cubes and the
+// search grid are the cube store of slio_cube_store.hpp (slio::lvx::CubeStore,
+// store_*), which A-LOAM's mapper (slio_aloam_map.hip) shares; slio_lvx derives
+// from it.
+//
 // so the VoxelGrids of all valid cubes of a class (:1197-1216, up to 125) are
 // one sequence of launches and one host wait.  Per cube the result is what
 // slio_scan_upload_voxel gives for that cube's cloud alone: the geometry
@@ -36,6 +41,7 @@
 #include <cstring>
 #include <vector>
 
+#include "slio_cube_store.hpp"
 #include "slio_device.hpp"
 #include "slio_frontend.h"
 #include "slio_livox.hpp"
@@ -47,7 +53,6 @@ using namespace slio::lvx;
 
 namespace {
 
-constexpr uint32_t kDrop = 0xFFFFFFFFu;
 constexpr uint64_t kDropKey = ~0ull;
 constexpr int kSortBits = 45;  // 32 voxel bits + 13 cube bits (kNum < 8191 = the dropped points' field)
 
@@ -55,12 +60,6 @@ __device__ __forceinline__ int32_t fkey(float f) {  // monotone float -> int
   const int32_t b = __float_as_int(f);
   return b >= 0 ? b : b ^ 0x7FFFFFFF;
 }
-
-struct CubeGeom {
-  float inv;
-  int minb[3];
-  int mul[3];
-};
 
 __global__ void k_lvx_append(const float* __restrict__ in, int64_t n, slio::LegoRot T, int cenI, int cenJ, int cenK,
                              float* __restrict__ x, float* __restrict__ y, float* __restrict__ z,
@@ -82,7 +81,7 @@ __global__ void k_lvx_append(const float* __restrict__ in, int64_t n, slio::Lego
 
 // the six shift loops (:493-713) composed: every cube moves by (di, dj, dk);
 // what leaves the array is dropped, what enters is empty
-__global__ void k_lvx_relabel(uint32_t* __restrict__ id, int64_t n, int di, int dj, int dk) {
+__global__ void k_lvx_relabel(uint32_t* __restrict__ id, int64_t n, int di, int dj, int dk, int kW, int kH, int kD) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t c = id[i];
@@ -366,35 +365,17 @@ inline int blocks(int64_t n) { return (int)((n + 255) / 256); }
 
 constexpr int64_t kMaxCells = (int64_t)1 << 24;
 
-struct Grid {
-  MapDev::Buf xyz, pts, start;  // the gathered map (n x 3), GridView's arrays
-  GridView view{};
-  int64_t n = 0;
-  bool built = false;
-};
-
 struct Scan {
   MapDev::Buf xyz, world, nbr_idx, nbr_sqd, coeff, sel, partial;
   int64_t n = 0;
   bool fed = false, passed = false;
 };
 
-struct Class {
-  float* xyz[2][3] = {};
-  uint32_t* id[2] = {};
-  int cur = 0;
-  int64_t n = 0;
-  std::vector<uint32_t> off = std::vector<uint32_t>(kNum + 1, 0u);  // host mirror
-};
-
 }  // namespace
 
-struct slio_lvx {
+struct slio_lvx : slio::lvx::CubeStore {  // (the store's class 2 holds the surf scan for its VoxelGrid)
   slio_lvx_params prm{};
   bool dev_counted = false;
-  hipStream_t stream = nullptr;
-  Class cls[3];  // corner map, surf map, and the surf scan as a one-cube map (its VoxelGrid)
-  Grid grid[2];
   Scan scan[2];
   float tobe[6] = {0}, aft[6] = {0}, last[6] = {0};  // transformTobeMapped / AftMapped / LastMapped
   // isDegenerate and matP are globals of the node: a call whose first turn has
@@ -405,27 +386,10 @@ struct slio_lvx {
   int32_t valid[125], surround[125];
   int32_t nvalid = 0, nsurround = 0;
   bool selected = false;
-  // work buffers, shared by the classes (one change runs at a time)
-  uint64_t* k0 = nullptr;
-  uint64_t* k1 = nullptr;
-  uint32_t *v0 = nullptr, *v1 = nullptr, *head = nullptr, *rank = nullptr, *off = nullptr;
-  int32_t* bb = nullptr;
-  CubeGeom* geom = nullptr;
-  uint8_t *filt = nullptr, *mode = nullptr;
-  uint2* seg = nullptr;
-  // pinned staging: the offset table coming back, the cube flags and the
-  // gather's segment table going out.  Every call that fills one ends with a
-  // wait on the stream, so the next call never overwrites a copy in flight.
-  uint32_t* h_off = nullptr;
-  uint8_t* h_filt = nullptr;
-  uint2* h_seg = nullptr;
-  MapDev::Buf tmp_sort, tmp_scan, in, out;
 };
 
-namespace {
-
-void lvx_free(slio_lvx* m) {
-  for (Class& c : m->cls)
+void slio::lvx::store_free(CubeStore* m) {
+  for (StoreClass& c : m->cls)
     for (int b = 0; b < 2; ++b) {
       for (int a = 0; a < 3; ++a)
         if (c.xyz[b][a]) (void)hipFree(c.xyz[b][a]);
@@ -436,11 +400,8 @@ void lvx_free(slio_lvx* m) {
     if (p) (void)hipFree(p);
   for (MapDev::Buf* b : {&m->tmp_sort, &m->tmp_scan, &m->in, &m->out})
     if (b->p) (void)hipFree(b->p);
-  for (Grid& g : m->grid)
+  for (StoreGrid& g : m->grid)
     for (MapDev::Buf* b : {&g.xyz, &g.pts, &g.start})
-      if (b->p) (void)hipFree(b->p);
-  for (Scan& s : m->scan)
-    for (MapDev::Buf* b : {&s.xyz, &s.world, &s.nbr_idx, &s.nbr_sqd, &s.coeff, &s.sel, &s.partial})
       if (b->p) (void)hipFree(b->p);
   if (m->h_off) (void)hipHostFree(m->h_off);
   if (m->h_filt) (void)hipHostFree(m->h_filt);
@@ -448,12 +409,15 @@ void lvx_free(slio_lvx* m) {
   if (m->stream) (void)hipStreamDestroy(m->stream);
 }
 
-// One change of class k: the N = stored + appended points (appended ones
-// already behind the stored ones, ids set) are sorted by cube, the cubes of
-// `filt` (device, kNum flags; null: none) are replaced by their VoxelGrid,
-// dropped points leave, and the offset table comes back: the ONE host wait.
-int rebuild(slio_lvx* m, int k, int64_t N, bool with_filter, float leaf, const char* who) {
-  Class& c = m->cls[k];
+static void lvx_free(slio_lvx* m) {
+  for (Scan& s : m->scan)
+    for (MapDev::Buf* b : {&s.xyz, &s.world, &s.nbr_idx, &s.nbr_sqd, &s.coeff, &s.sel, &s.partial})
+      if (b->p) (void)hipFree(b->p);
+  slio::lvx::store_free(m);
+}
+
+int slio::lvx::store_rebuild(CubeStore* m, int k, int64_t N, bool with_filter, float leaf, const char* who) {
+  StoreClass& c = m->cls[k];
   hipStream_t st = m->stream;
   if (N == 0) {
     c.n = 0;
@@ -500,26 +464,24 @@ int rebuild(slio_lvx* m, int k, int64_t N, bool with_filter, float leaf, const c
   return SLIO_OK;
 }
 
-// the flags of a cube list (checked by the caller) on the device; no wait
-int upload_filter(slio_lvx* m, const int32_t* list, int32_t n) {
+int slio::lvx::store_upload_filter(CubeStore* m, const int32_t* list, int32_t n) {
   std::memset(m->h_filt, 0, kNum);
   for (int i = 0; i < n; ++i) m->h_filt[list[i]] = 1;
   SLIO_HIP(hipMemcpyAsync(m->filt, m->h_filt, kNum, hipMemcpyHostToDevice, m->stream));
   return SLIO_OK;
 }
 
-bool list_ok(const int32_t* list, int32_t n) {
+bool slio::lvx::store_list_ok(const int32_t* list, int32_t n) {
   if (n < 0 || (n > 0 && !list)) return false;
   for (int i = 0; i < n; ++i)
     if (list[i] < 0 || list[i] >= kNum) return false;
   return true;
 }
 
-// the concatenation of the listed cubes (at most 125) of class k into m->out
-// (n x 3), *total points; no wait
-int gather(slio_lvx* m, int k, const int32_t* list, int32_t n, int64_t* total, MapDev::Buf* dst = nullptr) {
+int slio::lvx::store_gather(CubeStore* m, int k, const int32_t* list, int32_t n, int64_t* total,
+                            MapDev::Buf* dst) {
   if (!dst) dst = &m->out;
-  const Class& c = m->cls[k];
+  const StoreClass& c = m->cls[k];
   int nseg = 0;
   uint32_t pos = 0;
   for (int i = 0; i < n; ++i) {
@@ -541,8 +503,8 @@ int gather(slio_lvx* m, int k, const int32_t* list, int32_t n, int64_t* total, M
   return SLIO_OK;
 }
 
-int download(slio_lvx* m, int k, const int32_t* list, int32_t n, float* xyz, int64_t cap, int64_t* npts,
-             const char* who) {
+int slio::lvx::store_download(CubeStore* m, int k, const int32_t* list, int32_t n, float* xyz, int64_t cap,
+                              int64_t* npts, const char* who) {
   int64_t total = 0;
   for (int i = 0; i < n; ++i) total += m->cls[k].off[list[i] + 1] - m->cls[k].off[list[i]];
   if (npts) *npts = total;
@@ -551,14 +513,56 @@ int download(slio_lvx* m, int k, const int32_t* list, int32_t n, float* xyz, int
     set_error(std::string(who) + ": the output holds fewer points than the cubes");
     return SLIO_ECAPACITY;
   }
-  int rc = gather(m, k, list, n, &total);
+  int rc = store_gather(m, k, list, n, &total);
   if (rc || !total) return rc;
   SLIO_HIP(hipMemcpyAsync(xyz, m->out.p, 12 * (size_t)total, hipMemcpyDeviceToHost, m->stream));
   SLIO_HIP(hipStreamSynchronize(m->stream));
   return SLIO_OK;
 }
 
-}  // namespace
+int slio::lvx::store_shift(CubeStore* m, const int32_t shift[3], const char* who) {
+  for (int k = 0; k < 2; ++k) {
+    StoreClass& c = m->cls[k];
+    if (!c.n) continue;
+    k_lvx_relabel<<<blocks(c.n), 256, 0, m->stream>>>(c.id[c.cur], c.n, shift[0], shift[1], shift[2], m->W, m->H, m->D);
+    const int rc = store_rebuild(m, k, c.n, false, 0.0f, who);
+    if (rc) return rc;
+  }
+  return SLIO_OK;
+}
+
+hipError_t slio::lvx::store_alloc(CubeStore* m, size_t cap) {
+  hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
+  for (StoreClass& c : m->cls)
+    for (int b = 0; b < 2 && !e; ++b) {
+      for (int a = 0; a < 3 && !e; ++a) e = hipMalloc(&c.xyz[b][a], 4 * cap);
+      if (!e) e = hipMalloc(&c.id[b], 4 * cap);
+    }
+  if (!e) e = hipMalloc(&m->k0, 8 * cap);
+  if (!e) e = hipMalloc(&m->k1, 8 * cap);
+  if (!e) e = hipMalloc(&m->v0, 4 * cap);
+  if (!e) e = hipMalloc(&m->v1, 4 * cap);
+  if (!e) e = hipMalloc(&m->head, 4 * cap);
+  if (!e) e = hipMalloc(&m->rank, 4 * cap);
+  if (!e) e = hipMalloc(&m->off, 4 * (kNum + 1));
+  if (!e) e = hipMalloc(&m->bb, 4 * 8 * kNum);
+  if (!e) e = hipMalloc(&m->geom, sizeof(CubeGeom) * kNum);
+  if (!e) e = hipMalloc(&m->filt, kNum);
+  if (!e) e = hipMalloc(&m->mode, kNum);
+  if (!e) e = hipMalloc(&m->seg, sizeof(uint2) * (kMaxListed + 1));
+  if (!e) e = hipHostMalloc(&m->h_off, 4 * (kNum + 1), hipHostMallocDefault);
+  if (!e) e = hipHostMalloc(&m->h_filt, kNum, hipHostMallocDefault);
+  if (!e) e = hipHostMalloc(&m->h_seg, sizeof(uint2) * (kMaxListed + 1), hipHostMallocDefault);
+  return e;
+}
+
+void slio::lvx::store_clear(CubeStore* m) {
+  for (StoreClass& c : m->cls) {
+    c.n = 0;
+    std::fill(c.off.begin(), c.off.end(), 0u);
+  }
+  for (StoreGrid& g : m->grid) g.built = false;
+}
 
 #define LVX_CHECK(m, who)                                \
   do {                                                   \
@@ -598,28 +602,7 @@ int slio_lvx_create(slio_lvx_handle* out, const slio_lvx_params* p) {
   SLIO_HIP(hipSetDevice(p->device));
   slio_lvx* m = new slio_lvx();
   m->prm = *p;
-  const size_t cap = (size_t)p->max_points;
-  hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
-  for (Class& c : m->cls)
-    for (int b = 0; b < 2 && !e; ++b) {
-      for (int a = 0; a < 3 && !e; ++a) e = hipMalloc(&c.xyz[b][a], 4 * cap);
-      if (!e) e = hipMalloc(&c.id[b], 4 * cap);
-    }
-  if (!e) e = hipMalloc(&m->k0, 8 * cap);
-  if (!e) e = hipMalloc(&m->k1, 8 * cap);
-  if (!e) e = hipMalloc(&m->v0, 4 * cap);
-  if (!e) e = hipMalloc(&m->v1, 4 * cap);
-  if (!e) e = hipMalloc(&m->head, 4 * cap);
-  if (!e) e = hipMalloc(&m->rank, 4 * cap);
-  if (!e) e = hipMalloc(&m->off, 4 * (kNum + 1));
-  if (!e) e = hipMalloc(&m->bb, 4 * 8 * kNum);
-  if (!e) e = hipMalloc(&m->geom, sizeof(CubeGeom) * kNum);
-  if (!e) e = hipMalloc(&m->filt, kNum);
-  if (!e) e = hipMalloc(&m->mode, kNum);
-  if (!e) e = hipMalloc(&m->seg, sizeof(uint2) * 126);
-  if (!e) e = hipHostMalloc(&m->h_off, 4 * (kNum + 1), hipHostMallocDefault);
-  if (!e) e = hipHostMalloc(&m->h_filt, kNum, hipHostMallocDefault);
-  if (!e) e = hipHostMalloc(&m->h_seg, sizeof(uint2) * 126, hipHostMallocDefault);
+  const hipError_t e = store_alloc(m, (size_t)p->max_points);
   if (e) {
     set_error(std::string("slio_lvx_create: ") + hipGetErrorString(e));
     lvx_free(m);
@@ -644,17 +627,13 @@ int slio_lvx_destroy(slio_lvx_handle m) {
 
 int slio_lvx_clear(slio_lvx_handle m) {
   LVX_CHECK(m, "slio_lvx_clear");
-  for (Class& c : m->cls) {
-    c.n = 0;
-    std::fill(c.off.begin(), c.off.end(), 0u);
-  }
+  store_clear(m);
   m->cen[0] = 10;
   m->cen[1] = 5;
   m->cen[2] = 10;
   m->nvalid = m->nsurround = 0;
   m->selected = false;
   for (int k = 0; k < 2; ++k) {
-    m->grid[k].built = false;
     m->scan[k].fed = m->scan[k].passed = false;
     m->scan[k].n = 0;
   }
@@ -683,13 +662,7 @@ int slio_lvx_select_cubes(slio_lvx_handle m, const float transform[6], int32_t c
   }
   if (shift[0] || shift[1] || shift[2]) {
     SLIO_HIP(hipSetDevice(m->prm.device));
-    for (int k = 0; k < 2; ++k) {
-      Class& c = m->cls[k];
-      if (!c.n) continue;
-      k_lvx_relabel<<<blocks(c.n), 256, 0, m->stream>>>(c.id[c.cur], c.n, shift[0], shift[1], shift[2]);
-      const int rc = rebuild(m, k, c.n, false, 0.0f, "slio_lvx_select_cubes");
-      if (rc) return rc;
-    }
+    if (const int rc = store_shift(m, shift, "slio_lvx_select_cubes")) return rc;
   }
   m->grid[0].built = m->grid[1].built = false;  // (a new valid list: the maps are to be gathered again)
   std::memcpy(m->cen, cen, sizeof cen);
@@ -733,7 +706,7 @@ static int update_impl(slio_lvx_handle m, const float transform[6], const float*
     }
     valid = m->valid;
     nvalid = m->nvalid;
-  } else if (!list_ok(valid, nvalid)) {
+  } else if (!store_list_ok(valid, nvalid)) {
     set_error("slio_lvx_update_map: cube index out of range");
     return SLIO_EINVAL;
   }
@@ -748,7 +721,7 @@ static int update_impl(slio_lvx_handle m, const float transform[6], const float*
     return SLIO_OK;
   }
   SLIO_HIP(hipSetDevice(m->prm.device));
-  int rc = upload_filter(m, valid, nvalid);
+  int rc = store_upload_filter(m, valid, nvalid);
   if (rc) return rc;
   slio::LegoRot T;
   T.cr = slio::fcos(transform[0]);
@@ -763,7 +736,7 @@ static int update_impl(slio_lvx_handle m, const float transform[6], const float*
   const float* src[2] = {corner_xyz, surf_xyz};
   const float leaf[2] = {m->prm.leaf_corner, m->prm.leaf_surf};
   for (int k = 0; k < 2; ++k) {
-    Class& c = m->cls[k];
+    StoreClass& c = m->cls[k];
     if (nn[k]) {
       const float* d_src = src[k];
       if (!on_device) {
@@ -780,7 +753,7 @@ static int update_impl(slio_lvx_handle m, const float transform[6], const float*
                                                          m->cen[2], s[0] + c.n, s[1] + c.n, s[2] + c.n,
                                                          c.id[c.cur] + c.n);
     }
-    if ((rc = rebuild(m, k, c.n + nn[k], true, leaf[k], "slio_lvx_update_map"))) return rc;
+    if ((rc = store_rebuild(m, k, c.n + nn[k], true, leaf[k], "slio_lvx_update_map"))) return rc;
     if (counts) counts[k] = c.n;
     m->grid[k].built = false;  // the map the grid was built on has changed
   }
@@ -802,7 +775,7 @@ int slio_lvx_cube_sizes(slio_lvx_handle m, int kind, int32_t* sizes) {
     set_error("slio_lvx_cube_sizes: kind outside {0, 1} or null output");
     return SLIO_EINVAL;
   }
-  const Class& c = m->cls[kind];
+  const StoreClass& c = m->cls[kind];
   for (int i = 0; i < kNum; ++i) sizes[i] = (int32_t)(c.off[i + 1] - c.off[i]);
   return SLIO_OK;
 }
@@ -814,13 +787,13 @@ int slio_lvx_get_cube(slio_lvx_handle m, int kind, int32_t cube, float* xyz, int
     return SLIO_EINVAL;
   }
   SLIO_HIP(hipSetDevice(m->prm.device));
-  return download(m, kind, &cube, 1, xyz, cap, n, "slio_lvx_get_cube");
+  return store_download(m, kind, &cube, 1, xyz, cap, n, "slio_lvx_get_cube");
 }
 
 int slio_lvx_get_surround(slio_lvx_handle m, int kind, const int32_t* cubes, int32_t ncubes, float* xyz, int64_t cap,
                           int64_t* n) {
   LVX_CHECK(m, "slio_lvx_get_surround");
-  if ((kind != 0 && kind != 1) || cap < 0 || (cubes && (ncubes > 125 || !list_ok(cubes, ncubes))) ||
+  if ((kind != 0 && kind != 1) || cap < 0 || (cubes && (ncubes > 125 || !store_list_ok(cubes, ncubes))) ||
       (!cubes && ncubes != 0)) {
     set_error("slio_lvx_get_surround: kind outside {0, 1}, a cube outside the array, more than 125 cubes or "
               "negative capacity");
@@ -835,7 +808,7 @@ int slio_lvx_get_surround(slio_lvx_handle m, int kind, const int32_t* cubes, int
     ncubes = m->nsurround;
   }
   SLIO_HIP(hipSetDevice(m->prm.device));
-  return download(m, kind, cubes, ncubes, xyz, cap, n, "slio_lvx_get_surround");
+  return store_download(m, kind, cubes, ncubes, xyz, cap, n, "slio_lvx_get_surround");
 }
 
 int slio_lvx_get_centers(slio_lvx_handle m, int32_t cen[3]) {
@@ -866,13 +839,13 @@ int take_scan_outputs(slio_lvx* m, int k, int64_t n) {
   return SLIO_OK;
 }
 
-// the grid of class k over the concatenation of the valid cubes; one host
-// wait (the map's bounding box)
-int build_grid(slio_lvx* m, int k, const int32_t* valid, int32_t nvalid) {
-  Grid& g = m->grid[k];
+}  // namespace
+
+int slio::lvx::store_build_grid(CubeStore* m, int k, const int32_t* valid, int32_t nvalid, float h, const char* who) {
+  StoreGrid& g = m->grid[k];
   hipStream_t st = m->stream;
   int64_t total = 0;
-  int rc = gather(m, k, valid, nvalid, &total, &g.xyz);
+  int rc = store_gather(m, k, valid, nvalid, &total, &g.xyz);
   if (rc) return rc;
   g.n = total;
   g.view = GridView{};
@@ -885,7 +858,7 @@ int build_grid(slio_lvx* m, int k, const int32_t* valid, int32_t nvalid) {
   SLIO_HIP(hipMemcpyAsync(m->h_off, m->bb, sizeof init, hipMemcpyDeviceToHost, st));
   SLIO_HIP(hipStreamSynchronize(st));
   GridView v{};
-  v.h = k == 0 ? kCellCorner : kCellSurf;
+  v.h = h;
   v.inv_h = 1.0f / v.h;
   int dim[3];
   for (int a = 0; a < 3; ++a) {
@@ -899,7 +872,7 @@ int build_grid(slio_lvx* m, int k, const int32_t* valid, int32_t nvalid) {
     // the cell function of the kernels, on the host: same float operations
     const double top = std::floor((double)((fhi - v.o[a]) * v.inv_h));
     if (!(top >= 0.0 && top < 1.0e6)) {
-      set_error("slio_lvx_build_maps: map extent out of range");
+      set_error(std::string(who) + ": map extent out of range");
       return SLIO_ECAPACITY;
     }
     dim[a] = (int)top + 3;
@@ -909,12 +882,12 @@ int build_grid(slio_lvx* m, int k, const int32_t* valid, int32_t nvalid) {
   v.nz = dim[2];
   const int64_t ncells = (int64_t)dim[0] * dim[1] * dim[2];
   if (ncells > kMaxCells) {
-    set_error("slio_lvx_build_maps: the valid cubes span more than 2^24 search cells");
+    set_error(std::string(who) + ": the valid cubes span more than 2^24 search cells");
     return SLIO_ECAPACITY;
   }
   hipError_t e;
   if ((e = MapDev::take(g.pts, 16 * (size_t)total)) || (e = MapDev::take(g.start, 4 * (size_t)(ncells + 1)))) {
-    set_error(std::string("slio_lvx_build_maps: hipMalloc: ") + hipGetErrorString(e));
+    set_error(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
     return SLIO_ENOMEM;
   }
   v.n = total;
@@ -926,7 +899,7 @@ int build_grid(slio_lvx* m, int k, const int32_t* valid, int32_t nvalid) {
       (e = MapDev::take(m->tmp_sort, tb)) ||
       (e = hipcub::DeviceRadixSort::SortPairs(m->tmp_sort.p, tb, m->v0, m->v1, m->head, m->rank, (int)total, 0, bits,
                                               st))) {
-    set_error(std::string("slio_lvx_build_maps: sort: ") + hipGetErrorString(e));
+    set_error(std::string(who) + ": sort: " + hipGetErrorString(e));
     return SLIO_EDEVICE;
   }
   k_lvx_grid_pts<<<blocks(total), 256, 0, st>>>((const float*)g.xyz.p, m->rank, total, (float4*)g.pts.p);
@@ -937,6 +910,8 @@ int build_grid(slio_lvx* m, int k, const int32_t* valid, int32_t nvalid) {
   g.view = v;
   return SLIO_OK;
 }
+
+namespace {
 
 int run_pass(slio_lvx* m, int k, const float tf[6]) {
   Scan& sc = m->scan[k];
@@ -982,6 +957,27 @@ __global__ void k_lvx_take_xyz(const float* __restrict__ in, int64_t n, float* _
   out[3 * i + 2] = in[4 * i + 2];
 }
 
+}  // namespace
+
+void slio::lvx::store_take_xyz(const float* d_xyzi, int64_t n, float* d_xyz, hipStream_t st) {
+  if (n) k_lvx_take_xyz<<<blocks(n), 256, 0, st>>>(d_xyzi, n, d_xyz);
+}
+
+int slio::lvx::store_scan_voxel(CubeStore* m, const float* d_xyz, int64_t n, float leaf, MapDev::Buf* dst,
+                                int64_t* n_out, const char* who) {
+  StoreClass& tmp = m->cls[2];
+  tmp.cur = 0;
+  tmp.n = 0;
+  k_lvx_scan_in<<<blocks(n), 256, 0, m->stream>>>(d_xyz, n, tmp.xyz[0][0], tmp.xyz[0][1], tmp.xyz[0][2], tmp.id[0]);
+  const int32_t cube0 = 0;
+  int rc = store_upload_filter(m, &cube0, 1);
+  if (!rc) rc = store_rebuild(m, 2, n, true, leaf, who);
+  if (rc) return rc;
+  return store_gather(m, 2, &cube0, 1, n_out, dst);
+}
+
+namespace {
+
 // A feed is feed_begin, then the caller's copies on the stream -- the corner
 // cloud into scan[0].xyz, the surf cloud into m->in, both n x 3, from the host
 // (slio_lvx_feed_host) or from the registration's clouds (slio_lvx_feed_device)
@@ -1010,19 +1006,9 @@ int feed_finish(slio_lvx* m, int64_t n_corner, int64_t n_surf, int64_t counts[2]
   c0.n = n_corner;
   // surf: downSizeFilterSurf (:795-798) = the per-cube VoxelGrid of a one-cube map
   Scan& s1 = m->scan[1];
-  Class& tmp = m->cls[2];
-  tmp.cur = 0;
-  tmp.n = 0;
   if (n_surf) {
-    k_lvx_scan_in<<<blocks(n_surf), 256, 0, st>>>((const float*)m->in.p, n_surf, tmp.xyz[0][0], tmp.xyz[0][1],
-                                                  tmp.xyz[0][2], tmp.id[0]);
-    const int32_t zero = 0;
-    int rc = upload_filter(m, &zero, 1);
-    if (!rc) rc = rebuild(m, 2, n_surf, true, m->prm.leaf_surf, who);
-    if (rc) return rc;
-    const int32_t cube0 = 0;
     int64_t total = 0;
-    if ((rc = gather(m, 2, &cube0, 1, &total, &s1.xyz))) return rc;
+    if (int rc = store_scan_voxel(m, (const float*)m->in.p, n_surf, m->prm.leaf_surf, &s1.xyz, &total, who)) return rc;
     s1.n = total;
   } else {
     s1.n = 0;
@@ -1076,9 +1062,8 @@ int slio_lvx_feed_device(slio_lvx_handle m, void* reg, int64_t counts[2]) {
   const int64_t n_corner = v.n_corner, n_surf = v.n_surf;
   if (int rc = feed_begin(m, n_corner, n_surf, "slio_lvx_feed_device")) return rc;
   // (slio_lreg_run ended with a wait: the registration's clouds are complete)
-  if (n_corner)
-    k_lvx_take_xyz<<<blocks(n_corner), 256, 0, m->stream>>>(v.corner_xyzi, n_corner, (float*)m->scan[0].xyz.p);
-  if (n_surf) k_lvx_take_xyz<<<blocks(n_surf), 256, 0, m->stream>>>(v.surf_xyzi, n_surf, (float*)m->in.p);
+  store_take_xyz(v.corner_xyzi, n_corner, (float*)m->scan[0].xyz.p, m->stream);
+  store_take_xyz(v.surf_xyzi, n_surf, (float*)m->in.p, m->stream);
   SLIO_HIP(hipGetLastError());
   return feed_finish(m, n_corner, n_surf, counts, "slio_lvx_feed_device");
 }
@@ -1118,13 +1103,14 @@ int slio_lvx_build_maps(slio_lvx_handle m, const int32_t* valid, int32_t nvalid,
     }
     valid = m->valid;
     nvalid = m->nvalid;
-  } else if (nvalid > 125 || !list_ok(valid, nvalid)) {
+  } else if (nvalid > 125 || !store_list_ok(valid, nvalid)) {
     set_error("slio_lvx_build_maps: cube index out of range or more than 125 cubes");
     return SLIO_EINVAL;
   }
   SLIO_HIP(hipSetDevice(m->prm.device));
   for (int k = 0; k < 2; ++k) {
-    if (int rc = build_grid(m, k, valid, nvalid)) return rc;
+    const float h = k == 0 ? kCellCorner : kCellSurf;
+    if (int rc = store_build_grid(m, k, valid, nvalid, h, "slio_lvx_build_maps")) return rc;
     m->scan[k].passed = false;
     if (counts) counts[k] = m->grid[k].n;
   }

@@ -672,6 +672,177 @@ int slio_aloam_odom_host_run(const slio_aloam_odom_params* p, slio_aloam_odom_st
                              int64_t n_corner, const float* surf_last, int64_t n_surf,
                              slio_aloam_odom_result* res);
 
+/* ======================================================================
+ * A-LOAM laserMapping (src/A-LOAM/src/laserMapping.cpp; every path:line below
+ * is in that file unless said otherwise): the loop body of process() :326-893
+ * with the cloud outputs of :898-939 on the device, from the odometry's two
+ * last clouds and /laser_odom_to_init to /aft_mapped_to_init and the rolling
+ * map of 21 x 21 x 11 cubes of 50 m.  One sweep is
+ *   initial guess   :148-152  transformAssociateToMap
+ *   centre, shifts  :331-559  the centre cube from the DOUBLE t_w_curr, the
+ *                             six shift loops composed
+ *   selection       :566-583  i +- 2, j +- 2, k +- 1, k innermost: at most 75
+ *                             cubes, each both valid and surround
+ *   down-sampling   :597-607  VoxelGrid of both incoming clouds (leaf_corner,
+ *                             leaf_surf; 0.4 / 0.8 at :993-997)
+ *   gate            :613      more than 10 corner and more than 50 surf map
+ *                             points in the valid cubes, or no optimisation
+ *   two passes      :622-824  each one association at the current pose, then
+ *                             one solve of at most 4 iterations (:811):
+ *     pointAssociateToMap :160-168  q * p + t in double, rounded to float
+ *     5-NN            :644, :722  exact, gate sqd[4] < 1.0
+ *     line fit        :648-691  centre, covariance, 3 x 3 eigen-solve, the
+ *                               test lambda2 > 3 lambda1, a / b = centre +- 0.1 d
+ *     plane fit       :725-766  5 x 3 A x = -1, n = x / |x|, d = 1 / |x|, all
+ *                               five neighbours within 0.2
+ *     factors         lidarFactor.hpp:12-67 (double end points), :127-164,
+ *                     analytic Jacobians in [d theta, d t], HuberLoss(0.1)
+ *   transformUpdate :155-158  in every case
+ *   map update      :835-892  both stacks at the solved pose into their cubes,
+ *                             then the VoxelGrid of every valid cube
+ * The cube store is livox_mapping's (slio_lvx_*: one SoA per class sorted by
+ * cube, one pass and one host wait per change), its extents set to 21 x 21 x
+ * 11.  The solve is enqueued whole -- per pass: associate (one launch per
+ * class), evaluate, control, then 4 x (evaluate, control), the kernels of a
+ * finished solve returning at once -- with no host wait in between: 24
+ * launches for the two passes.  Host waits per sweep: 2 for the two
+ * VoxelGrids of the incoming clouds, 0 to 2 for a shift (one per non-empty
+ * class), 2 for the bounding boxes of the two search grids, 1 for the result,
+ * 2 for the map update: 7, and up to 9 on a sweep that shifts.
+ *
+ * Stated departures from the reference:
+ *  - the solve is not Ceres: this library's Levenberg-Marquardt of
+ *    slio_aloam_odom_*, parity with Ceres' own iterates unpinned;
+ *  - the eigen-solve (cyclic Jacobi, 8 sweeps) and the column-pivoting QR are
+ *    this library's text (csrc/slio_aloam_map.hpp): parity with Eigen's
+ *    SelfAdjointEigenSolver and with Eigen's summation order is unpinned; the
+ *    sign of the line direction is free, it leaves J^T J and J^T r unchanged;
+ *  - the 5-NN is exact with ties to the lower index in the concatenation of
+ *    the valid cubes (FLANN's order among equal distances is unpinned);
+ *  - a VoxelGrid sums a voxel's points in the stored order (slio_lvx_*'s);
+ *  - the map stores x, y, z only: A-LOAM's intensity only reaches published
+ *    clouds (slio_aloam_map_register_cloud keeps it);
+ *  - a zero covariance, a rank-deficient plane system or a plane normal that
+ *    is not finite gives no factor and is counted as degenerate (the
+ *    reference would hand Ceres a NaN, or a plane through collinear points);
+ *  - a point that does not transform to a finite coordinate is dropped at
+ *    append;
+ *  - the sums run over factor slots (corner stack, then surf stack) in a
+ *    fixed order: per 256 slots 32 strided partials in ascending slot, added
+ *    in ascending lane, then the same over the groups of 256;
+ *  - publishers, path, TF and the message queue's dropping of old frames
+ *    (:317-320) are not restated.
+ * ====================================================================== */
+typedef struct slio_aloam_map* slio_aloam_map_handle;
+typedef struct slio_aloam_map_host* slio_aloam_map_host_handle;
+
+typedef struct slio_aloam_map_params {
+  int32_t device;
+  int32_t max_points; /* capacity of each class of the map, >= 1 */
+  int32_t max_scan;   /* capacity of each incoming cloud, 1 .. 400000 */
+  float leaf_corner;  /* mapping_line_resolution (:993), 0.4 */
+  float leaf_surf;    /* mapping_plane_resolution (:994), 0.8 */
+  int32_t reserved[3];
+} slio_aloam_map_params;
+
+typedef struct slio_aloam_map_result {
+  double q_w_curr[4], t_w_curr[3];         /* /aft_mapped_to_init */
+  double q_wmap_wodom[4], t_wmap_wodom[3]; /* after transformUpdate */
+  int32_t center[3], shift[3];             /* the centre cube after the shifts; turns of the `< 3` loops minus
+                                              those of the `>= dim - 3` loops */
+  int32_t map_size[2];                     /* laserCloudCornerFromMapNum, laserCloudSurfFromMapNum */
+  int32_t stack_size[2];                   /* the two down-sampled clouds */
+  int32_t optimized;                       /* the gate of :613 opened: pass[] is filled */
+  int32_t nvalid;                          /* laserCloudValidNum */
+  slio_aloam_odom_pass pass[2];            /* corner / plane: factors; few: always 0 */
+} slio_aloam_map_result;
+
+/* device 0, max_points 2^21, max_scan 400000, leaves 0.4 / 0.8. */
+int slio_aloam_map_params_default(slio_aloam_map_params* p);
+/* EINVAL: max_points < 1, max_scan outside 1 .. 400000, a leaf that is not
+ * finite and positive, negative device (before any device call), no such device. */
+int slio_aloam_map_create(slio_aloam_map_handle* out, const slio_aloam_map_params* p);
+int slio_aloam_map_destroy(slio_aloam_map_handle h);
+/* Back to the state after create: empty map, centres 10 / 10 / 5, identity poses. */
+int slio_aloam_map_reset(slio_aloam_map_handle h);
+/* One sweep from laserCloudCornerLast / laserCloudSurfLast on the host, n x
+ * {x, y, z, intensity} each, and the odometry's pose.  EINVAL (before any
+ * device call): a negative size, a null cloud with a size > 0, a null or
+ * non-finite pose, a zero q_wodom_curr, a null result; ECAPACITY: a cloud
+ * beyond max_scan, or stored + incoming points of a class beyond max_points.
+ * The handle is unchanged after a refused call. */
+int slio_aloam_map_run(slio_aloam_map_handle h, const float* corner_last, int64_t n_corner, const float* surf_last,
+                       int64_t n_surf, const double q_wodom_curr[4], const double t_wodom_curr[3],
+                       slio_aloam_map_result* res);
+/* The same from the odometry's device-resident last clouds
+ * (slio_aloam_odom_get_view), device to device.  EINVAL also for a view of
+ * another device. */
+int slio_aloam_map_run_view(slio_aloam_map_handle h, const slio_aloam_odom_view* v, const double q_wodom_curr[4],
+                            const double t_wodom_curr[3], slio_aloam_map_result* res);
+/* laserCloudFullRes into the map frame at the last sweep's pose (:929-933):
+ * n x {x, y, z, intensity}, intensity kept.  on_device: xyzi is a device
+ * pointer of the handle's device.  ESTATE before a sweep. */
+int slio_aloam_map_register_cloud(slio_aloam_map_handle h, const float* xyzi, int64_t n, int on_device, float* out);
+/* One cube (n x 3), the sizes of all 4851 cubes, the cubes of the last
+ * selection concatenated (:899-905, one class), a whole class in cube order
+ * (:916-921, one class), the down-sampled cloud of the last sweep.  kind 0
+ * corner, 1 surf.  xyz null: the size only.  ESTATE before a sweep;
+ * ECAPACITY: cap < n. */
+int slio_aloam_map_get_cube(slio_aloam_map_handle h, int kind, int32_t cube, float* xyz, int64_t cap, int64_t* n);
+int slio_aloam_map_cube_sizes(slio_aloam_map_handle h, int kind, int32_t* sizes);
+int slio_aloam_map_get_surround(slio_aloam_map_handle h, int kind, float* xyz, int64_t cap, int64_t* n);
+int slio_aloam_map_get_map(slio_aloam_map_handle h, int kind, float* xyz, int64_t cap, int64_t* n);
+int slio_aloam_map_get_stack(slio_aloam_map_handle h, int kind, float* xyz, int64_t cap, int64_t* n);
+/* -- lockstep entries, for tests -- */
+/* One association of the last sweep's stacks at (q, t) against the map that
+ * sweep was solved against.  ESTATE before a sweep, or where that sweep's
+ * gate stayed shut (no search grid was built). */
+int slio_aloam_map_associate(slio_aloam_map_handle h, const double q[4], const double t[3]);
+/* Per slot (corner stack, then surf stack) of the last association: kind (0
+ * none, 1 edge, 2 plane, 3 degenerate, 4 rejected by the fit), the record (6
+ * doubles: a, b or n, d, 0, 0), the five neighbours' indices in the
+ * concatenation of the valid cubes and their squared distances (-1 / +inf
+ * where the gate stayed shut).  Any output may be null.  ESTATE before an
+ * association; ECAPACITY: cap_slots < n. */
+int slio_aloam_map_get_association(slio_aloam_map_handle h, uint8_t* kind, double* rec, int32_t* nbr_idx,
+                                   float* nbr_sqd, int64_t cap_slots, int32_t* n);
+/* The factors of the last association at (q, t): A, g, cost as
+ * slio_aloam_odom_evaluate, counts = {edge, plane, degenerate, outliers}. */
+int slio_aloam_map_evaluate(slio_aloam_map_handle h, const double q[4], const double t[3], double A[21], double g[6],
+                            double* cost, int32_t counts[4]);
+/* -- host only, callable without a GPU -- */
+/* :222-223: the high-frequency pose from q / t_wmap_wodom and an odometry pose. */
+int slio_aloam_map_predict(const double q_wmap_wodom[4], const double t_wmap_wodom[3], const double q_wodom_curr[4],
+                           const double t_wodom_curr[3], double q_w_curr[4], double t_w_curr[3]);
+/* :331-583 at t_w_curr: cen (laserCloudCenWidth / Height / Depth) is updated;
+ * list holds up to 75 cube indices. */
+int slio_aloam_map_host_select(const double t_w_curr[3], int32_t cen[3], int32_t center[3], int32_t shift[3],
+                               int32_t* list, int32_t* n);
+/* The fits on five neighbours (15 doubles, nearest first).  Return the kind
+ * (1 edge / 2 plane, 3 degenerate, 4 rejected) or a negative error.  lam / vec
+ * (3 / 9 doubles, vec row-major with the eigenvectors in its columns; either
+ * may be null): the eigen-solve of the covariance.  x (3 doubles, may be
+ * null): the solution of A x = -1 before normalisation. */
+int slio_aloam_map_host_fit_line(const double* nb, double a[3], double b[3], double* lam, double* vec);
+int slio_aloam_map_host_fit_plane(const double* nb, double normal[3], double* d, double* x);
+/* The sums over n slots (points n x 3, kinds, records) at (q, t), in the stated order. */
+int slio_aloam_map_host_evaluate(const float* xyz, const uint8_t* kind, const double* rec, int64_t n,
+                                 const double q[4], const double t[3], double A[21], double g[6], double* cost,
+                                 int32_t counts[4]);
+/* The whole node on the host: the same entries on a host-resident map (p->device
+ * is not read); the 5-NN is brute force over the valid cubes.  get_association
+ * reports the last pass's. */
+int slio_aloam_map_host_create(slio_aloam_map_host_handle* out, const slio_aloam_map_params* p);
+int slio_aloam_map_host_destroy(slio_aloam_map_host_handle h);
+int slio_aloam_map_host_run(slio_aloam_map_host_handle h, const float* corner_last, int64_t n_corner,
+                            const float* surf_last, int64_t n_surf, const double q_wodom_curr[4],
+                            const double t_wodom_curr[3], slio_aloam_map_result* res);
+int slio_aloam_map_host_get_cube(slio_aloam_map_host_handle h, int kind, int32_t cube, float* xyz, int64_t cap,
+                                 int64_t* n);
+int slio_aloam_map_host_get_stack(slio_aloam_map_host_handle h, int kind, float* xyz, int64_t cap, int64_t* n);
+int slio_aloam_map_host_get_association(slio_aloam_map_host_handle h, uint8_t* kind, double* rec, int32_t* nbr_idx,
+                                        float* nbr_sqd, int64_t cap_slots, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,10 @@
             into association and solve, correspondences, iterations, launches and waits,
             registration plus odometry per sweep, the host restatement beside it (only
             when named)
+  aloam_map A-LOAM's laserMapping (AloamMapping: slio_aloam_map_*) on the same two inputs as
+            two alternating sweeps of a moving sensor with a drifting odometry pose: ms per
+            mapping call, map and stack sizes, factors, iterations, launches and waits, the
+            host restatement beside it (only when named)
   livox_reg livox_mapping's scanRegistration (LivoxScanRegistration: slio_lreg_*) on a
             dense continuous-curve frame of about 24,000 returns: ms per registration,
             the counts, the host restatement beside it; then process_cloud (sensor's
@@ -953,8 +957,65 @@ def aloam_odom(reps=20):
                       "host_waits_per_odometry_call": 1, "kernel_times": "not measured"}), flush=True)
 
 
+def aloam_map(reps=20):
+    """A-LOAM's laserMapping (AloamMapping: slio_aloam_map_*) on aloam_odom's
+    two inputs and two sweeps.  The mapper takes each sweep's
+    cornerPointsLessSharp and surfPointsLessFlat (the odometry's last clouds)
+    and the sweep's true pose with an offset of 2 mrad and (3, -2, 1) cm as the
+    odometry pose; the two sweeps alternate, so after the first two calls every
+    call is a full mapping call (two associations, two solves, the map update)
+    on a map that has stopped growing.  Host wall clock around synchronous
+    calls, mean of `reps` after a warm-up of four; the same calls through the
+    host restatement (one thread, brute-force 5-NN) beside it, mean of 2."""
+    from agi_lidar_slam_amd import synth
+    from agi_lidar_slam_amd.aloam import AloamMapping, AloamMappingHost, register_host
+    upper, lower = 2.0 - np.arange(33) / 3.0, -8.83 - np.arange(1, 32) / 2.0
+    inputs = (("vlp16_h1800", 16, -15.0 + 2.0 * np.arange(16), 1800),
+              ("hdl64_h2083", 64, np.concatenate([upper, lower]), 2083))
+    rows = []
+    for name, n_scans, beams, horizon in inputs:
+        sw = synth.make_spinning_sweep(beams, horizon=horizon)
+        a = np.ascontiguousarray(np.stack([sw["x"], sw["y"], sw["z"]], 1), np.float32)
+        c, s_ = np.cos(0.02), np.sin(0.02)
+        d = a.astype(np.float64) - np.array([0.15, 0.04, 0.0])
+        b = np.ascontiguousarray(np.stack([c * d[:, 0] + s_ * d[:, 1], -s_ * d[:, 0] + c * d[:, 1], d[:, 2]], 1),
+                                 np.float32)
+        clouds = []
+        for x in (a, b):
+            w = register_host(x, n_scans=n_scans)
+            clouds.append((w["cornerPointsLessSharp"], w["surfPointsLessFlat"]))
+        poses = (([0.0, 0.0, np.sin(0.001), np.cos(0.001)], [0.03, -0.02, 0.01]),
+                 ([0.0, 0.0, np.sin(0.011), np.cos(0.011)], [0.18, 0.02, 0.01]))
+        dev, host = AloamMapping(), AloamMappingHost()
+        for k in range(4):
+            r_dev, r_host = dev.process(*clouds[k % 2], *poses[k % 2]), host.process(*clouds[k % 2], *poses[k % 2])
+        same = r_dev == r_host
+        t0 = time.perf_counter()
+        for k in range(4, 4 + reps):
+            r_dev = dev.process(*clouds[k % 2], *poses[k % 2])
+        ms_dev = (time.perf_counter() - t0) * 1e3 / reps
+        t0 = time.perf_counter()
+        for k in range(4, 6):
+            r_host = host.process(*clouds[k % 2], *poses[k % 2])
+        ms_host = (time.perf_counter() - t0) * 1e3 / 2
+        ps = r_dev["passes"]
+        rows.append({"input": name, "last_points": [int(len(clouds[1][0])), int(len(clouds[1][1]))],
+                     "stack": r_dev["stack_size"], "map": r_dev["map_size"], "ms_per_mapping_call": ms_dev,
+                     "factors": [[p["corner"], p["plane"]] for p in ps], "iterations": [p["iterations"] for p in ps],
+                     "stops": [p["stop"] for p in ps], "ms_host_restatement": ms_host,
+                     "host_same_bits_as_device": bool(same)})
+        dev.close()
+        host.close()
+    print(json.dumps({"bench": "aloam_map", "inputs": rows,
+                      "launches_of_the_solve": "24 (per pass 2 x associate, 5 x evaluate, 5 x control)",
+                      "host_waits_per_mapping_call": "7 (2 scan VoxelGrids, 2 grid boxes, 1 result, 2 map updates)",
+                      "kernel_times": "not measured"}), flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["mapping", "preproc", "s2m"]
+    if "aloam_map" in what:
+        aloam_map()
     if "aloam_odom" in what:
         aloam_odom()
     if "aloam_reg" in what:
