@@ -3,4 +3,4 @@
 The device path lives in ``libslio.so`` (HIP kernels + C-ABI, include/slio.h);
 ``esekf`` mirrors the reference's ``esekfom::esekf`` interface on top of it.
 """
-__all__ = ["build", "synth", "livox_map", "livox_reg"]
+__all__ = ["build", "synth", "livox_map", "livox_reg", "lio_livox"]

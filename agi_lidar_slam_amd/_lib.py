@@ -178,6 +178,7 @@ _IP = C.POINTER(C.c_int32)
 _I64P = C.POINTER(C.c_int64)
 _U8P = C.POINTER(C.c_uint8)
 _U16P = C.POINTER(C.c_uint16)
+_U32P = C.POINTER(C.c_uint32)
 
 # name -> (restype, argtypes); every symbol include/*.h declares
 class SlioImuSample(C.Structure):
@@ -223,6 +224,21 @@ class SlioLvxParams(C.Structure):
 class SlioLregParams(C.Structure):
     """slio_lreg_params (include/slio_frontend.h)."""
     _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class SlioLlregParams(C.Structure):
+    """slio_llreg_params (include/slio_frontend.h)."""
+    _fields_ = [("device", C.c_int32), ("max_points", C.c_int32), ("n_scans", C.c_int32), ("lidar_type", C.c_int32),
+                ("num_curv_size", C.c_int32), ("num_flat", C.c_int32), ("part_num", C.c_int32),
+                ("distance_faraway", C.c_float), ("flat_threshold", C.c_float), ("break_corner_dis", C.c_float),
+                ("lidar_nearest_dis", C.c_float), ("kdtree_corner_outlier_dis", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+class SlioLlregView(C.Structure):
+    """slio_llreg_view (include/slio_frontend.h)."""
+    _fields_ = [("cloud", C.c_void_p), ("corner", C.c_void_p), ("surf", C.c_void_p), ("n_cloud", C.c_int32),
+                ("n_corner", C.c_int32), ("n_surf", C.c_int32), ("device", C.c_int32)]
 
 
 class SlioAloamParams(C.Structure):
@@ -555,6 +571,21 @@ SIGNATURES = {
     "slio_aloam_map_host_get_cube": (C.c_int, [_P, C.c_int, C.c_int32, _FP, C.c_int64, _I64P]),
     "slio_aloam_map_host_get_stack": (C.c_int, [_P, C.c_int, _FP, C.c_int64, _I64P]),
     "slio_aloam_map_host_get_association": (C.c_int, [_P, _U8P, _DP, _IP, _FP, C.c_int64, _IP]),
+    # include/slio_frontend.h (LIO-Livox ScanRegistration)
+    "slio_llreg_params_default": (C.c_int, [C.POINTER(SlioLlregParams)]),
+    "slio_llreg_create": (C.c_int, [C.POINTER(_P), C.POINTER(SlioLlregParams)]),
+    "slio_llreg_destroy": (C.c_int, [_P]),
+    "slio_llreg_run": (C.c_int, [_P, _FP, _U8P, _U8P, _U32P, C.c_int64, _IP]),
+    "slio_llreg_run_pc2": (C.c_int, [_P, _FP, C.c_int64, _IP]),
+    "slio_llreg_get_cloud": (C.c_int, [_P, C.c_int, _FP, C.c_int64]),
+    "slio_llreg_get_lines": (C.c_int, [_P, _IP, _IP]),
+    "slio_llreg_get_flags": (C.c_int, [_P, C.c_int32, _IP, _U8P, _FP, C.c_int64]),
+    "slio_llreg_get_view": (C.c_int, [_P, C.POINTER(SlioLlregView)]),
+    "slio_llreg_tiles": (C.c_int, [_IP, _IP, _IP, _IP]),
+    "slio_llreg_extract_host": (C.c_int, [C.POINTER(SlioLlregParams), _FP, _U8P, _U8P, _U32P, C.c_int64, _FP, _FP,
+                                          _FP, _IP, _IP, _IP, _IP, _U8P, _FP]),
+    "slio_llreg_extract_pc2_host": (C.c_int, [C.POINTER(SlioLlregParams), _FP, C.c_int64, _FP, _FP, _FP, _IP, _IP,
+                                              _IP, _IP, _U8P, _FP]),
 }
 
 _lib = None
@@ -615,6 +646,10 @@ def u8ptr(a: np.ndarray):
 
 def u16ptr(a: np.ndarray):
     return a.ctypes.data_as(_U16P)
+
+
+def u32ptr(a: np.ndarray):
+    return a.ctypes.data_as(_U32P)
 
 
 def i64ptr(a: np.ndarray):

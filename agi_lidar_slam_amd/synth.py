@@ -513,3 +513,26 @@ def make_scan_curve(scene: Scene, pos, yaw: float, n_rays: int, k0: int = 0, see
     body = dl[ok] * tt[:, None]
     refl = rng.integers(1, 200, int(ok.sum())).astype(np.float64)
     return np.ascontiguousarray(np.concatenate([body, refl[:, None]], 1), dtype=np.float32)
+
+
+def make_livox_lines(scene: Scene, pos, yaw: float, n_lines: int, rays_per_line: int, k0: int = 0, seed: int = 0,
+                     period_ns: int = 100_000_000, furniture: bool = True) -> dict:
+    """A multi-line Livox frame as livox_ros_driver's CustomMsg carries it, for
+    LIO-Livox's ScanRegistration: n_lines curves of make_scan_curve (line l
+    starts rays_per_line * l + 311 * l rays further along the figure, so the
+    lines sweep different parts of the scene), interleaved point by point in
+    firing order as the sensor's lasers fire in turn; a line that runs out of
+    returns early simply stops.  reflectivity is the curve's, uint8;
+    offset_time rises evenly to period_ns at the last point.  Returns
+    dict(xyz (n, 3) float32, reflectivity uint8, line uint8, offset_time
+    uint32)."""
+    curves = [make_scan_curve(scene, pos, yaw, rays_per_line, k0=k0 + (rays_per_line + 311) * l, seed=seed + 7 * l,
+                              furniture=furniture) for l in range(n_lines)]
+    slot = np.concatenate([np.arange(len(c), dtype=np.int64) * n_lines + l for l, c in enumerate(curves)])
+    order = np.argsort(slot, kind="stable")
+    pts = np.concatenate(curves, 0)[order]
+    line = np.concatenate([np.full(len(c), l, np.uint8) for l, c in enumerate(curves)])[order]
+    n = len(pts)
+    off = (np.arange(1, n + 1, dtype=np.float64) * (period_ns / max(n, 1))).astype(np.uint32)
+    return dict(xyz=np.ascontiguousarray(pts[:, :3], np.float32), reflectivity=pts[:, 3].astype(np.uint8),
+                line=np.ascontiguousarray(line), offset_time=off)

@@ -843,6 +843,135 @@ int slio_aloam_map_host_get_stack(slio_aloam_map_host_handle h, int kind, float*
 int slio_aloam_map_host_get_association(slio_aloam_map_host_handle h, uint8_t* kind, double* rec, int32_t* nbr_idx,
                                         float* nbr_sqd, int64_t cap_slots, int32_t* n);
 
+/* ======================================================================
+ * LIO-Livox ScanRegistration for Use_seg = 0 (src/LIO-Livox/src/lio/
+ * ScanRegistration.cpp, "SR" below, and LidarFeatureExtractor.cpp, every other
+ * path:line below): lidarCallBackHorizon -> FeatureExtract :1218-1291 and
+ * lidarCallBackPc2 (SR:61-93) -> FeatureExtract_Mid :1352-1401, with
+ * detectFeaturePoint :93-614 once per line, on the device.  One opaque handle
+ * owns the buffers of one device and one stream.  A run is
+ *   ingest     :1237-1263  (SR:69-84 for Pc2) the line and x filters, normal_x,
+ *                          the per-line lists in the message's order
+ *   finite     :112-130    the finite points of each line, order kept
+ *   per point  :151-203    depth, the two ray angles, K, curvature, diffR
+ *   picking    :205-297    PartNum parts per line, each sorted twice (stable),
+ *                          the flag loop (3 and the neighbour marks 1) and the
+ *                          pick loop (2, and 300 by reflectivity)
+ *   lines      :301-403    the strided pass (i += 4 after a flat right side):
+ *                          150 where two flat sides meet at a sharp angle
+ *   breaks     :407-578    100 by the depth-ordering rules, demoted to 101 by
+ *                          the front / back fan test
+ *   collect    :591-613    2 -> surf, 100 / 150 -> corner, the near points out
+ *   write-back :1273-1290  the labels 1 (corner) and 2 (surf) on the cloud, the
+ *                          two feature clouds in cloud order
+ * as nine launches, whatever n, on one stream and ONE host wait, the copy of
+ * the counts.  The three clouds stay on the device until the next run.
+ *
+ * A cloud point is 8 floats: {x, y, z, intensity, normal_x, normal_y, normal_z,
+ * curvature = 0}.  normal_x is the time fraction; normal_y the line, as the
+ * int's bits in the CustomMsg path (_int_as_float, :1254) and as a float value
+ * in the Pc2 path (SR:82); normal_z the label 0 / 1 / 2.
+ *
+ * Kept as written: the label of a line's feature idx (an index into the
+ * line's FINITE points) lands on vlines[line][idx], an index into ALL its
+ * points (:1276, :1280), so a line with non-finite points labels other points
+ * of that line; K in the picking loops is the K of the line's last loop
+ * position, so NumCurvSize is accepted and never has an effect; temp_depth
+ * reads i - k in both fan loops (:535, :554).
+ *
+ * Undefined in the reference, defined here: cloudAngle[] and CloudFeatureFlag[]
+ * (:96, :102, never initialised) are zero before use; thNumCurvSize (raced on
+ * by the per-line threads) is a per-line value; a line of more than 20000
+ * points after ingest (:96) is SLIO_ECAPACITY, nothing is truncated; the Pc2
+ * entries (line = i % 4) want n_scans >= 4, SLIO_EINVAL otherwise (:1372
+ * indexes past vlines); an empty message (:1238 calls back()) gives zero
+ * counts.  plane_judge (:473, :512) is dead and not built.  A diffR or a
+ * curvature that is NaN (a NaN or infinite intensity in the Pc2 cloud, which
+ * only x, y and z are tested for, reaches the diffR of up to seven points
+ * around it; coordinates near FLT_MAX do it to the curvature) leaves the
+ * reference's two sorts to the order of their swaps; here NaN sorts as one
+ * class after every number, ties by position, on the host and on the device.
+ * Errors as in slio.h; argument errors are reported before any device call.
+ * ====================================================================== */
+typedef struct slio_llreg* slio_llreg_handle;
+
+typedef struct slio_llreg_params {
+  int32_t device;
+  int32_t max_points;            /* input capacity, 1 .. 120000 = 6 lines of 20000 (:96)      */
+  int32_t n_scans;               /* Used_Line, 1 .. 6                                         */
+  int32_t lidar_type;            /* Lidar_Type 0 / 1: x < 0.01 dropped; 2: fabs(x) < 0.01      */
+  int32_t num_curv_size;         /* NumCurvSize: accepted, never has an effect (see above)    */
+  int32_t num_flat;              /* NumFlat >= 0                                              */
+  int32_t part_num;              /* PartNum, 1 .. 20000                                       */
+  float distance_faraway;        /* DistanceFaraway                                           */
+  float flat_threshold;          /* FlatThreshold                                             */
+  float break_corner_dis;        /* BreakCornerDis                                            */
+  float lidar_nearest_dis;       /* LidarNearestDis                                           */
+  float kdtree_corner_outlier_dis; /* KdTreeCornerOutlierDis: read by no path built here      */
+  int32_t reserved[4];
+} slio_llreg_params;
+
+/* What a consumer on the device reads (a later estimator): device pointers to
+ * the three clouds of the last run, n x 8 floats each. */
+typedef struct slio_llreg_view {
+  const float* cloud;
+  const float* corner;
+  const float* surf;
+  int32_t n_cloud, n_corner, n_surf, device;
+} slio_llreg_view;
+
+/* config/horizon_config.yaml: device 0, max_points 120000, 6 lines, type 0,
+ * NumCurvSize 2, DistanceFaraway 100, NumFlat 3, PartNum 150, FlatThreshold
+ * 0.02, BreakCornerDis 1, LidarNearestDis 1, KdTreeCornerOutlierDis 0.2. */
+int slio_llreg_params_default(slio_llreg_params* p);
+/* The LidarFeatureExtractor constructor (:3-23).  EINVAL: a field outside the
+ * ranges above, a threshold that is not finite, no such device. */
+int slio_llreg_create(slio_llreg_handle* out, const slio_llreg_params* p);
+int slio_llreg_destroy(slio_llreg_handle h);
+/* lidarCallBackHorizon's FeatureExtract (:1218-1291) on one CustomMsg as SoA
+ * arrays: xyz[n * 3], reflectivity[n], line[n], offset_time[n].  counts =
+ * {laserCloud, laserConerFeature, laserSurfFeature} sizes.  EINVAL: n < 0, a
+ * null array with n > 0, null counts; ECAPACITY: n > max_points, or a line of
+ * more than 20000 points after ingest (the handle then has no run). */
+int slio_llreg_run(slio_llreg_handle h, const float* xyz, const uint8_t* reflectivity, const uint8_t* line,
+                   const uint32_t* offset_time, int64_t n, int32_t counts[3]);
+/* lidarCallBackPc2 (SR:61-93) with FeatureExtract_Mid (:1352-1401) on xyzi[n *
+ * 4]: the x filter of lidar_type, normal_x = float(i) / float(n), line = i % 4
+ * with i the index before the filter.  counts[0] is laser_cloud_custom's size.
+ * EINVAL also when the handle's n_scans < 4. */
+int slio_llreg_run_pc2(slio_llreg_handle h, const float* xyzi, int64_t n, int32_t counts[3]);
+/* kind 0: the full cloud with its labels (:1285 reads it), 1: laserConerFeature
+ * (:1286), 2: laserSurfFeature (:1289); counts[kind] x 8 floats.  ESTATE
+ * without a run; ECAPACITY when cap (in points) is less. */
+int slio_llreg_get_cloud(slio_llreg_handle h, int kind, float* points, int64_t cap);
+/* vlines[l]->size() (:1261) and the number of finite points among them (:132)
+ * for l < 6 (zero past n_scans).  Either may be NULL. */
+int slio_llreg_get_lines(slio_llreg_handle h, int32_t line_size[6], int32_t finite_size[6]);
+/* For tests: line l's CloudFeatureFlag[0 .. finite_size[l]) after the break-
+ * point loop, 1 where the line-feature loop (:301) visited the position, and
+ * the finite points themselves (x 4 floats).  Any may be NULL; cap in points. */
+int slio_llreg_get_flags(slio_llreg_handle h, int32_t l, int32_t* flags, uint8_t* visited, float* xyzi, int64_t cap);
+int slio_llreg_get_view(slio_llreg_handle h, slio_llreg_view* v);
+/* The shapes of the kernels, for tests that put seams on them: the chain kernel
+ * (one workgroup per line) gives thread t the loop positions [5 + t *
+ * chain_per_thread, 5 + (t + 1) * chain_per_thread); the picking kernel
+ * resolves a part of up to pick_fast points in registers and a longer one
+ * serially on one lane; every other kernel works on block inputs per workgroup. */
+int slio_llreg_tiles(int32_t* chain_per_thread, int32_t* chain_per_workgroup, int32_t* pick_fast, int32_t* block);
+/* -- host only, callable without a GPU -- */
+/* The same two paths as their literal serial loops (p->device and max_points
+ * are not read).  cloud / corner / surf: n x 8 floats; flags / visited / lines
+ * (x 4 floats): the lines' finite points concatenated in line order, n entries
+ * at most; line_size / finite_size as slio_llreg_get_lines.  Every output but
+ * counts may be NULL. */
+int slio_llreg_extract_host(const slio_llreg_params* p, const float* xyz, const uint8_t* reflectivity,
+                            const uint8_t* line, const uint32_t* offset_time, int64_t n, float* cloud, float* corner,
+                            float* surf, int32_t counts[3], int32_t* line_size, int32_t* finite_size, int32_t* flags,
+                            uint8_t* visited, float* lines);
+int slio_llreg_extract_pc2_host(const slio_llreg_params* p, const float* xyzi, int64_t n, float* cloud, float* corner,
+                                float* surf, int32_t counts[3], int32_t* line_size, int32_t* finite_size,
+                                int32_t* flags, uint8_t* visited, float* lines);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,10 @@
             the counts, the host restatement beside it; then process_cloud (sensor's
             cloud to pose) over a short drive: ms per call, of which the registration
             (only when named)
+  lio_livox_reg LIO-Livox's ScanRegistration (LioLivoxScanRegistration: slio_llreg_*) on a
+            24,000-point 6-line frame with the Horizon parameters and a 20,000-point 4-line
+            frame with the Mid-360 parameters: ms per FeatureExtract, the counts, the host
+            restatement beside each (only when named)
 One JSON line per measurement (host wall clock around synchronous calls)."""
 import ctypes as C
 import json
@@ -860,6 +864,50 @@ def livox_reg(n_rays=31000, frames_n=8, reps=20):
         h.close()
 
 
+def lio_livox_reg(reps=50):
+    """LIO-Livox's ScanRegistration (LioLivoxScanRegistration: slio_llreg_*) on
+    synth.make_livox_lines frames: 6 lines of 4000 returns with
+    horizon_config.yaml's parameters and 4 lines of 5000 with
+    mid360_config.yaml's, and the first again with PartNum 1, where every part
+    takes the picking kernel's serial path.  ms per FeatureExtract (the staging copy, the upload,
+    nine launches and the wait for the counts; host wall clock around the
+    synchronous call, mean of `reps` after a warm-up), the counts, and the same
+    message through the host restatement (slio_llreg_extract_host, one
+    thread) beside it."""
+    from agi_lidar_slam_amd import synth
+    from agi_lidar_slam_amd.lio_livox import HORIZON, MID360, LioLivoxScanRegistration, extract_host, tiles
+    seed = 20261020
+    scene = synth.make_scene(seed, 1000)
+    pos = np.array([synth.SENSOR_STREET[0] - 3.0, synth.SENSOR_STREET[1] + 0.2, 1.6])
+    rows = []
+    # the third row reaches the picking kernel's serial path: one part per line
+    for name, cfg, per_line in (("horizon_6x4000", HORIZON, 4000), ("mid360_4x5000", MID360, 5000),
+                                ("horizon_6x4000_partnum_1", dict(HORIZON, part_num=1), 4000)):
+        n_lines = cfg["n_scans"]
+        msg = synth.make_livox_lines(scene, pos, 0.0, n_lines, int(per_line * 1.4), seed=seed + 5)
+        keep = np.zeros(len(msg["line"]), bool)
+        for l in range(n_lines):
+            keep[np.nonzero(msg["line"] == l)[0][:per_line]] = True
+        msg = {k: np.ascontiguousarray(v[keep]) for k, v in msg.items()}
+        reg = LioLivoxScanRegistration(**cfg)
+        reg.run(**msg)                                      # warm-up
+        long_parts = cfg["part_num"] == 1
+        ms_dev, counts = t_ms(lambda: reg.run(**msg), 10 if long_parts else reps)
+        ms_host, host = t_ms(lambda: extract_host(reg.params, **msg), 2 if long_parts else 5)
+        full, corner, surf = reg.FeatureExtract(**msg)
+        same = all(np.array_equal(a.view(np.uint32), b.view(np.uint32))
+                   for a, b in ((full, host["cloud"]), (corner, host["corner"]), (surf, host["surf"])))
+        same = bool(same and all(np.array_equal(reg.flags(l)[0], host["flags"][l]) for l in range(n_lines)))
+        rows.append({"input": name, "points": int(len(msg["xyz"])), "ms_per_feature_extract": ms_dev,
+                     "counts_cloud_corner_surf": [int(v) for v in counts], "ms_host_restatement": ms_host,
+                     "host_same_bits_as_device": same})
+        reg.close()
+    print(json.dumps({"bench": "lio_livox_reg", "inputs": rows, "launches_per_message": 9,
+                      "host_waits_per_message": 1, "picking": "one wavefront per line, parts in order",
+                      "tiles_chain_per_thread_workgroup_pick_fast_block": list(tiles()),
+                      "kernel_times": "not measured"}), flush=True)
+
+
 def aloam_reg(reps=20):
     """A-LOAM's scanRegistration (AloamScanRegistration: slio_aloam_*) on a
     VLP-16 sweep at horizon 1800 and a 64-line sweep at horizon 2083
@@ -1020,6 +1068,8 @@ if __name__ == "__main__":
         aloam_odom()
     if "aloam_reg" in what:
         aloam_reg()
+    if "lio_livox_reg" in what:
+        lio_livox_reg()
     if "livox_reg" in what:
         livox_reg()
     if "livox_map" in what:
