@@ -2070,6 +2070,12 @@ struct FuseArgs {
   double* gsup;
   uint32_t* garrive;     // [0] the ranks' arrivals; [2..3] gflag (u64): (seq << 32) | done << 31 | passes
   int32_t gseq;          // the update's sequence number
+  // single-rank fused pass: the launch has one workgroup more than chunks (the
+  // last block index), which stages the control block, collects the segment
+  // rows as they become ready and runs the filter step (reducer_pass); 0: the
+  // workgroup that completes the 64th row does (SLIO_NO_REDUCER, the group,
+  // rows-only and persistent paths)
+  int32_t reducer;
   // persistent update (k_update_persist): 8 replicas (one per XCD, 128 B
   // apart) of the flag (gseq << 32) | done << 31 | passes its filter step
   // publishes after each pass; null otherwise
@@ -2080,6 +2086,9 @@ struct FuseArgs {
 };
 constexpr int kGoFlagStride = 16;  // uint64 words between the replicas
 constexpr int kSegCnt = 16;
+// a segment row's counter word once the row's sum is in seg_out (reducer path;
+// no count of chunk arrivals reaches it)
+constexpr uint32_t kRowReady = 0x80000000u;
 constexpr int kCountWords = kSegCnt + kNSeg;
 constexpr int kKcCount = 8;  // count[8..9]: certified / searched queries (slio_debug_knn_cert)
 
@@ -2120,7 +2129,7 @@ __device__ __forceinline__ void prefetch_ctl(const IkfCtl* __restrict__ hsrc, Ik
 // After the chunk partial is stored (sc1): arrival on the chunk's segment row;
 // the last arrival sums the row, and the last row runs the filter step.
 // Every thread of the workgroup calls it.
-template <int NT, int D, bool WT = false>
+template <int NT, int D, bool WT = false, bool RED = false>
 __device__ __forceinline__ void fused_tail(StepLds& L, int& bcast, const FuseArgs& fa, IkfCtl* ctl,
                                            const double* chunk_part, int64_t chunk, int iter) {
   const int t = threadIdx.x;
@@ -2153,6 +2162,26 @@ __device__ __forceinline__ void fused_tail(StepLds& L, int& bcast, const FuseArg
       for (int j = 0; j < kJ; ++j) acc = acc + v[j];
     }
     st_sc1(fa.seg_out + b * SLIO_NPROD + t, acc);
+  }
+  if constexpr (RED) {
+    // a launch with a reducer workgroup (reducer_pass) hands the row to it
+    // here: the row's stores drained, then the row's counter word becomes its
+    // ready mark (a write-through store; an atomic exchange in its place
+    // measured the same).  Nothing is waited for and no arrival value comes back.
+    drain_stores();
+    __syncthreads();
+    if (t == 0) st_sc1_u32(fa.cnt + kSegCnt + b, kRowReady);
+#ifdef SLIO_SOLVE_STAMP
+    // (the latest of the 64 rows' stamps: workgroups on different XCDs write
+    // them, so each is an agent-scope maximum over the words the reducer
+    // zeroed at its start)
+    if (t == 0) {
+      ts[2] = wall_clock64();
+      for (int k = 0; k < 3; ++k)
+        __hip_atomic_fetch_max(&g_sstamp[16 + k], ts[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#endif
+    return;
   }
   if (t == 0) reset_counter(fa.cnt + kSegCnt + b);
   drain_stores();
@@ -2245,6 +2274,233 @@ __device__ __forceinline__ void fused_tail(StepLds& L, int& bcast, const FuseArg
 #endif
 }
 
+// The reducer workgroup of a single-rank fused pass (FuseArgs::reducer): the
+// launch's last block, with no chunk of its own.  It is the consumer of the
+// pass's sums from the start of the launch, so everything the filter step
+// needs that does not depend on the last chunk is in LDS or registers before
+// that chunk arrives:
+//   - the control list and flags, staged into LDS at once (first pass: read
+//     from the caller's mapped host block and written through to the HBM
+//     copy, which the later passes' launches read; later passes: from HBM);
+//   - dx_new = x [-] x_propagated, formed here from the staged iterate (the
+//     arithmetic of ikf_dx_new);
+//   - the segment rows: every wavefront polls the 64 rows' counter words, lane
+//     b the word of row b (one sc1 load per wavefront and round, two rounds in
+//     flight, so a mark is seen a fraction of a round trip after it lands --
+//     no barrier and no LDS between a mark and the load of its row).  A row
+//     whose word reads kRowReady is loaded (one 8-B load per thread) into a
+//     register of the thread that holds it.  Thread (h, k), h = t / 128,
+//     k = t % 128 < 91, holds rows 32 h .. 32 h + 31 of product k; the
+//     register is chosen by a statically unrolled, wave-uniform branch.  The
+//     words are reset once all four wavefronts have seen all 64 marks.
+// After the last row's mark is seen, one round trip (that row's 91 sums)
+// precedes the totals -- super rows and total in final_step's order, so the
+// same bits -- and ikf_step.  No search workgroup waits for this one, and it
+// waits only for workgroups of its own launch (each running, finished, or
+// dispatched whatever this one does): no deadlock.  The wait is bounded as
+// k_update_persist's (wait_ticks; the mapped block's timeout word).
+struct ReducerLds {
+  StepLds L;
+  int stop;  // a wavefront's wait gave up
+};
+template <int NT, int D, bool DEVPOSE>
+__device__ __forceinline__ void reducer_pass(ReducerLds& rl, const FuseArgs& fa, int iter) {
+  static_assert(NT == 256 && kNSeg == 64 && SLIO_NPROD <= 128, "reducer: 2 x 128 threads hold 32 rows each");
+  StepLds& L = rl.L;
+  IkfCtl* ctl = fa.ctl;
+  const int t = threadIdx.x;
+#ifdef SLIO_SOLVE_STAMP
+  // reducer start / control block staged / last row seen / its sums loaded
+  // (g_sstamp[44..47]); totals and the step's phases as in ikf_step
+  if (t == 0) g_sstamp[44] = wall_clock64();
+  if (t < 3) __hip_atomic_store(&g_sstamp[16 + t], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+  const unsigned long long lim = fa.wait_ticks ? fa.wait_ticks : 100000000ull;
+  if (lim == 1) {  // give up at once (the test hook of slio_debug_wait_limit)
+    if (t == 0) {
+      __hip_atomic_store(&fa.hblk->timeout, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      st_sc1_u32(reinterpret_cast<uint32_t*>(&ctl->done), 1u);  // the update's later launches exit
+    }
+    return;
+  }
+  const unsigned long long t0 = wall_clock64();
+  {
+    // the control list, every load issued before the first LDS store
+    constexpr int nC = CtlList<D>::total, kC = (nC + NT - 1) / NT;
+    const bool first = fa.pre != nullptr;
+    const double* src = reinterpret_cast<const double*>(first ? fa.pre : (const IkfCtl*)ctl);
+    const uint32_t* fsrc = reinterpret_cast<const uint32_t*>(first ? &fa.pre->converge : &ctl->converge);
+    double cv[kC];
+#pragma unroll
+    for (int u = 0; u < kC; ++u) {
+      const int e = t + u * NT;
+      cv[u] = e < nC ? (first ? ld_sys(src + ctl_src<D>(e)) : ld_sc1(src + ctl_src<D>(e))) : 0.0;
+    }
+    uint32_t fl = 0, seq = 0;
+    if (t < 8) fl = first ? ld_sys_u32(fsrc + t) : ld_sc1_u32(fsrc + t);
+    if (first && t == 9) seq = ld_sys_u32(reinterpret_cast<const uint32_t*>(&fa.pre->seq));
+#pragma unroll
+    for (int u = 0; u < kC; ++u) {
+      const int e = t + u * NT;
+      if (e < nC) {
+        ctl_dst<D>(L, e) = cv[u];
+        if (first) st_sc1(reinterpret_cast<double*>(ctl) + ctl_src<D>(e), cv[u]);  // keep it in HBM
+      }
+    }
+    if (t < 8) {
+      L.fl[t] = (int32_t)fl;
+      if (first) st_sc1_u32(reinterpret_cast<uint32_t*>(&ctl->converge) + t, fl);
+    }
+    if (first && t == 8) st_sc1_u32(reinterpret_cast<uint32_t*>(&ctl->singular), 0u);
+    if (first && t == 9) st_sc1_u32(reinterpret_cast<uint32_t*>(&ctl->seq), seq);
+    if (t == 0) rl.stop = 0;
+  }
+  __syncthreads();
+  if constexpr (DEVPOSE) {
+    // dx_new of the iterate this pass runs at (pass 0: zeros, from the host)
+    if (t < 24) {
+      if (t < 3 || t >= 9) {
+        const double* xs = reinterpret_cast<const double*>(&L.x);
+        const double* ps = reinterpret_cast<const double*>(&L.xprop);
+        const double v = xs[state_off(t)] - ps[state_off(t)];
+        L.dxn[t] = v;
+        st_sc1(&ctl->dxn[t], v);
+      }
+    } else if (t == 32 || t == 64) {
+      const int u = t == 32;
+      const double* q1 = u ? L.x.rli : L.x.rot;
+      const double* q2 = u ? L.xprop.rli : L.xprop.rot;
+      double d[3];
+      so3_boxminus(Quat{q1[0], q1[1], q1[2], q1[3]}, Quat{q2[0], q2[1], q2[2], q2[3]}, d);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        L.dxn[3 + 3 * u + j] = d[j];
+        st_sc1(&ctl->dxn[3 + 3 * u + j], d[j]);
+      }
+    }
+  }
+#ifdef SLIO_SOLVE_STAMP
+  if (t == 0) g_sstamp[45] = wall_clock64();
+#endif
+  // the rows, as they become ready
+  const int half = t >> 7, k = t & 127;
+  const bool holder = k < SLIO_NPROD;
+  // The lane's address in rows 5, 16 and 27 of its 32, held over the loop
+  // (opaque to the compiler): every row of the 32 lies within a load's
+  // immediate offset (+-4 KiB) of one of them, so a row's load below is one
+  // instruction that writes nothing but the row's register -- an address
+  // formed in that register would make the loads of one round wait for each
+  // other.  Lanes >= 91 load product 0 and drop it.
+  constexpr int kAnchor[3] = {5, 16, 27};
+  const char* anchor[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    anchor[q] = reinterpret_cast<const char*>(fa.seg_out + (size_t)(32 * half + kAnchor[q]) * SLIO_NPROD +
+                                              (holder ? k : 0));
+    asm volatile("" : "+v"(anchor[q]));
+  }
+  double r[32];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) r[j] = 0.0;
+  // One poll's answer: the rows newly marked ready; those of this wavefront's
+  // half are loaded.  (The half of the mask in a scalar register: uniform
+  // branches.)
+  const uint32_t* cw = fa.cnt + kSegCnt + (t & 63);
+  const int hsh = 32 * __builtin_amdgcn_readfirstlane(half);
+  unsigned long long seen = 0;
+  auto take = [&](uint32_t c) {
+    const unsigned long long m = __ballot(c == kRowReady) & ~seen;
+    seen |= m;
+    const uint32_t mh = (uint32_t)(m >> hsh);
+#pragma unroll
+    for (int j = 0; j < 32; ++j)
+      if ((mh >> j) & 1u) {
+        constexpr int kRowBytes = SLIO_NPROD * (int)sizeof(double);
+        const int q = j < 11 ? 0 : (j < 22 ? 1 : 2);
+        static_assert(11 * kRowBytes / 2 < 4096, "reducer: rows within a load's immediate offset of an anchor");
+        r[j] = ld_sc1(reinterpret_cast<const double*>(anchor[q] + (j - kAnchor[q]) * kRowBytes));
+      }
+  };
+  // two polls in flight: the next one is issued before this one's answer is
+  // waited for.  The clock is read now and then only (a read costs about as
+  // much as a poll).
+  bool gave_up = false;
+  uint32_t ca = ld_sc1_u32(cw), cb;
+  for (uint32_t round = 1;; ++round) {
+    cb = ld_sc1_u32(cw);
+    take(ca);
+    if (seen == ~0ull) break;
+    ca = ld_sc1_u32(cw);
+    take(cb);
+    if (seen == ~0ull) break;
+    if ((round & 255u) == 0 && wall_clock64() - t0 > lim) {
+      gave_up = true;
+      break;
+    }
+  }
+#ifdef SLIO_SOLVE_STAMP
+  if (t == 0) g_sstamp[46] = g_sstamp[32 + ((iter + 1) & 3)] = wall_clock64();
+#endif
+  if (gave_up && (t & 63) == 0) rl.stop = 1;
+  // the 8 super rows and the pass total in final_step's order (rows 0..7 of a
+  // super row, then super rows 0..7)
+  double a = 0.0;
+  double sp[4] = {0.0, 0.0, 0.0, 0.0};
+  if (holder) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      double v = r[s * kSuperSeg];
+#pragma unroll
+      for (int q = 1; q < kSuperSeg; ++q) v = v + r[s * kSuperSeg + q];
+      sp[s] = v;
+    }
+#ifdef SLIO_SOLVE_STAMP
+    if (t == 0) g_sstamp[47] = wall_clock64();
+#endif
+    if (half) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) L.sup[4 + s][k] = sp[s];
+    } else {
+      a = ((sp[0] + sp[1]) + sp[2]) + sp[3];
+    }
+  }
+  __syncthreads();
+  if (rl.stop) {
+    if (t == 0) {
+      __hip_atomic_store(&fa.hblk->timeout, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      st_sc1_u32(reinterpret_cast<uint32_t*>(&ctl->done), 1u);  // the update's later launches exit
+    }
+    return;
+  }
+  if (t < 64) reset_counter(fa.cnt + kSegCnt + t);  // (every wavefront has seen every mark)
+  if (holder) {
+    // (slio_super_download reads them)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) fa.super_out[(4 * half + s) * SLIO_NPROD + k] = sp[s];
+  }
+  if (holder && !half) {
+#pragma unroll
+    for (int s = 4; s < SLIO_NSUPER; ++s) a = a + L.sup[s][k];
+    L.tot[k] = a;
+    if (k < SLIO_NHTH)
+      L.Mt[k] = a / fa.R;
+    else if (k < SLIO_NHTH + 12)
+      L.hR[k - SLIO_NHTH] = a / fa.R;
+  }
+  __syncthreads();
+  SSTAMP(4);
+  if (!L.fl[F_DONE]) ikf_step<NT, D, false>(ctl, fa.hblk, fa.R, iter, fa.maxit, L);
+  if (t == 0) {
+    // the pass's number of far queries (slio_far_queries); queue reset
+    st_sc1_u32(fa.cnt + 6, ld_sc1_u32(fa.cnt + 5));
+    st_sc1_u32(fa.cnt + 4, 0u);
+    st_sc1_u32(fa.cnt + 5, 0u);
+#ifdef SLIO_SOLVE_STAMP
+    g_sstamp[25 + ((iter + 1) & 3)] = wall_clock64();  // per pass: the filter step's end
+#endif
+  }
+}
+
 // One h_share_model search pass over one 128-point chunk.
 // Phase 1 (kNN): LPQ lanes per scan point find the exact 5-NN; results go to
 // LDS.  Phase 2 (fit): one lane per point reloads the 5 neighbours (L2-hot),
@@ -2293,14 +2549,16 @@ template <int NT>
 union PassLds {
   SearchLds<NT> s;
   StepLds L;
+  ReducerLds r;  // (r.L is L)
 };
+static_assert(sizeof(ReducerLds) <= sizeof(SearchLds<kSolveThreads>), "the reducer adds no LDS to a pass");
 
 // The pass body: the search (or, reuse, the reuse pass's rows), the chunk's
 // products and (FUSE) the fused tail.  pose: the pass's pose; DEVPOSE: a
 // pass after the first of a device-resident update (certificates, dx_new);
 // PERS: a pass of the persistent update, whose control-block reads are
 // write-through (the launch's earlier passes wrote it).
-template <int LPQ, int U, bool SPHERE, bool DEVPOSE, bool FUSE, int FD, bool PERS>
+template <int LPQ, int U, bool SPHERE, bool DEVPOSE, bool FUSE, int FD, bool PERS, bool RED = false>
 __device__ __forceinline__ void search_pass_body(PassLds<search_block<LPQ>()>& lds, int& fuse_bcast,
                                                  const MapView& map, const ScanDev& scan, const PoseDev& pose,
                                                  const PassCfg& cfg, const PassOut& out, const FuseArgs& fa,
@@ -2309,7 +2567,7 @@ __device__ __forceinline__ void search_pass_body(PassLds<search_block<LPQ>()>& l
   // kNN certificates (passes after the first of a device-resident update,
   // 2 lanes per query, 3x3x3 block first): see the certificate below
   constexpr bool KC = DEVPOSE && LPQ == 2 && !SPHERE;
-  if (DEVPOSE) ikf_dx_new<PERS>(cfg.ctl);
+  if (DEVPOSE && !RED) ikf_dx_new<PERS>(cfg.ctl);  // (RED: the reducer forms its own)
   constexpr int QPP = NT / LPQ;               // queries per kNN pass
   constexpr int PASSES = SLIO_CHUNK / QPP;    // kNN passes per chunk
   static_assert(SLIO_CHUNK % QPP == 0, "chunk must be a multiple of queries/pass");
@@ -2921,7 +3179,7 @@ __device__ __forceinline__ void search_pass_body(PassLds<search_block<LPQ>()>& l
     const double pv = chunk_sums_256(rows, part, cfg.mfma);
     if (tid < SLIO_NPROD) st_sc1(out.chunk_part + chunk * SLIO_NPROD + tid, pv);  // read by another workgroup
     if (tid == 0) STAMP(3);
-    fused_tail<NT, FD, PERS>(lds.L, fuse_bcast, fa, fa.ctl, out.chunk_part, chunk, iter);
+    fused_tail<NT, FD, PERS, RED>(lds.L, fuse_bcast, fa, fa.ctl, out.chunk_part, chunk, iter);
   } else {
     if constexpr (NT == 256) {
       const double pv = chunk_sums_256(rows, part, cfg.mfma);
@@ -2933,11 +3191,12 @@ __device__ __forceinline__ void search_pass_body(PassLds<search_block<LPQ>()>& l
   }
 }
 
-template <int LPQ, int U, bool SPHERE, bool DEVPOSE, bool FUSE = false, int FD = 6>
+template <int LPQ, int U, bool SPHERE, bool DEVPOSE, bool FUSE = false, int FD = 6, bool RED = false>
 __global__ __launch_bounds__(search_block<LPQ>(), SPHERE ? 2 : 4) void k_search_pass(
     const MapView map, const ScanDev scan, const PoseDev pose_arg, const PassCfg cfg,
     const PassOut out, const FuseArgs fa) {
   static_assert(!FUSE || search_block<LPQ>() == kSolveThreads, "fused pass: 256 threads");
+  static_assert(!RED || FUSE, "a reducer workgroup: fused single-rank passes only");
 #ifdef SLIO_SOLVE_STAMP
   if (FUSE && blockIdx.x == 0 && threadIdx.x == 0) {
     g_sstamp[20] = wall_clock64();
@@ -2945,7 +3204,7 @@ __global__ __launch_bounds__(search_block<LPQ>(), SPHERE ? 2 : 4) void k_search_
   }
 #endif
   if constexpr (FUSE && !DEVPOSE)
-    if (blockIdx.x == 0 && fa.pre) prefetch_ctl<FD>(fa.pre, fa.ctl);
+    if (!RED && blockIdx.x == 0 && fa.pre) prefetch_ctl<FD>(fa.pre, fa.ctl);  // (RED: the reducer stages it)
   // DEVPOSE: pose and pass selection come from the device-resident update.
   // A fused pass runs whichever pass the update wants (search or reuse,
   // ctl->search_now = converge, esekfom.hpp:138): one launch per pass in the
@@ -2955,11 +3214,18 @@ __global__ __launch_bounds__(search_block<LPQ>(), SPHERE ? 2 : 4) void k_search_
     return;
   __shared__ PassLds<search_block<LPQ>()> lds;
   __shared__ int fuse_bcast;
+  if constexpr (RED) {
+    // the block after the last chunk's: the pass's reducer
+    if ((int64_t)blockIdx.x == cfg.c_end - cfg.c_begin) {
+      reducer_pass<kSolveThreads, FD, DEVPOSE>(lds.r, fa, fa.iter);
+      return;
+    }
+  }
   const PoseDev pose = DEVPOSE ? pose_of_ctl(cfg.ctl, cfg.pass_idx) : pose_arg;
   bool reuse = false;
   if constexpr (FUSE && DEVPOSE) reuse = !cfg.ctl->search_now;
-  search_pass_body<LPQ, U, SPHERE, DEVPOSE, FUSE, FD, false>(lds, fuse_bcast, map, scan, pose, cfg, out, fa,
-                                                            reuse, fa.iter);
+  search_pass_body<LPQ, U, SPHERE, DEVPOSE, FUSE, FD, false, RED>(lds, fuse_bcast, map, scan, pose, cfg, out,
+                                                                 fa, reuse, fa.iter);
 }
 
 // The persistent update (single rank, fused passes): ONE launch runs every
@@ -3273,6 +3539,7 @@ static void load_switches(Ctx& c) {
   c.sw.event_wait = env_on("SLIO_EVENT_WAIT");
   c.sw.no_kc = env_on("SLIO_NO_KNN_CERT");
   c.sw.persist = env_on("SLIO_PERSIST");
+  c.sw.no_reducer = env_on("SLIO_NO_REDUCER");
 }
 static inline int64_t mono_ns() {
   timespec ts;
@@ -3681,9 +3948,19 @@ int enqueue_pass(Ctx& c, const PoseDev* Parg, IkfCtl* ctl, int which, int extrin
       // (D = 6, or 12 with extrinsic estimation) runs in this launch, no
       // k_super_sums; a later pass is a search or a reuse pass as the update
       // decides on the device
-#define SLIO_LAUNCH_FUSED(DEV, D)                                                                           \
-  hipExtLaunchKernelGGL(k_search_pass<2, SLIO_SEARCH_U, false, DEV, true, D>, nb, dim3(kSolveThreads), 0, \
-                        c.stream, ev.first, ev.second, 0, mv, s, P, cfg, o, *fuse)
+#define SLIO_LAUNCH_FUSED_R(DEV, D, RED)                                                               \
+  hipExtLaunchKernelGGL(k_search_pass<2, SLIO_SEARCH_U, false, DEV, true, D, RED>,                       \
+                        dim3((unsigned)nblk + (RED ? 1u : 0u)), dim3(kSolveThreads), 0, c.stream, ev.first, \
+                        ev.second, 0, mv, s, P, cfg, o, *fuse)
+      // (with a reducer: the instantiation that has one, and one workgroup
+      // after the chunks')
+#define SLIO_LAUNCH_FUSED(DEV, D)         \
+  do {                                    \
+    if (fuse->reducer)                    \
+      SLIO_LAUNCH_FUSED_R(DEV, D, true);  \
+    else                                  \
+      SLIO_LAUNCH_FUSED_R(DEV, D, false); \
+  } while (0)
 #define SLIO_LAUNCH_PERSIST(D)                                                                    \
   hipExtLaunchKernelGGL(k_update_persist<SLIO_SEARCH_U, D>, nb, dim3(kSolveThreads), 0, c.stream, ev.first, \
                         ev.second, 0, mv, s, P, cfg, o, *fuse, persist)
@@ -3704,6 +3981,7 @@ int enqueue_pass(Ctx& c, const PoseDev* Parg, IkfCtl* ctl, int which, int extrin
           SLIO_LAUNCH_FUSED(false, 6);
       }
 #undef SLIO_LAUNCH_FUSED
+#undef SLIO_LAUNCH_FUSED_R
 #undef SLIO_LAUNCH_PERSIST
     } else
     switch (c.prm.lanes_per_query * 2 + (sph ? 1 : 0)) {
@@ -7384,15 +7662,19 @@ struct UpdateRun {
         }
         SLIO_HSTAMP(c, 2);
       }
-      const FuseArgs fa{c.ctl,   p0 ? (const IkfCtl*)c.d_hctl : nullptr,
-                        c.d_seg, c.d_super,
-                        c.ctl,   c.d_hctl,
-                        c.count, R,
-                        i,       maxit,
-                        num_chunks(c.n), kNSeg,
-                        0,       1,
-                        nullptr, nullptr,
-                        0};
+      FuseArgs fa{c.ctl,   p0 ? (const IkfCtl*)c.d_hctl : nullptr,
+                  c.d_seg, c.d_super,
+                  c.ctl,   c.d_hctl,
+                  c.count, R,
+                  i,       maxit,
+                  num_chunks(c.n), kNSeg,
+                  0,       1,
+                  nullptr, nullptr,
+                  0};
+      // the filter step on a workgroup of its own (reducer_pass) unless
+      // SLIO_NO_REDUCER=1: then on the last workgroup to arrive
+      fa.reducer = c.sw.no_reducer ? 0 : 1;
+      fa.wait_ticks = c.wait_ticks;
       int rc = enqueue_pass(c, p0 ? &pose0 : nullptr, c.ctl, which, ext, &sa, true, false, nullptr, &fa);
       if (rc) return rc;
       if (p0) SLIO_HSTAMP(c, 3);
@@ -7541,7 +7823,7 @@ struct UpdateRun {
       // and others never will: back to zero before the next update
       reset_update_counters(c);
       if (to) {
-        set_error("slio_ikf_update_device: a device-side wait gave up (persistent pass flag or group gate, "
+        set_error("slio_ikf_update_device: a device-side wait gave up (reducer rows, persistent pass flag or group gate, "
                   "> 1 s) " + st + "; the handle's arrival counters were reset");
         return SLIO_ETIMEOUT;
       }
@@ -7877,8 +8159,8 @@ static int group_update(slio_handle* hs, int n, slio_state* x, double P[576], do
                           C,       kNSeg / n,
                           r * (SLIO_NSUPER / n), n,
                           c0.gsup, c0.garrive,
-                          seq,     nullptr,
-                          c0.wait_ticks};
+                          seq,     0,
+                          nullptr, c0.wait_ticks};
         rc = enqueue_pass(cr, p0 ? &runs[r].pose0 : nullptr, c0.ctl, which, extrinsic_est, &sa, true, false,
                           nullptr, &fa);
         if (!rc && hipGetLastError() != hipSuccess) {

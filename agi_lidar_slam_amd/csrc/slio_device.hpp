@@ -246,6 +246,7 @@ struct Ctx {
     bool event_wait = false;  // SLIO_EVENT_WAIT: wait on a completion event
     bool no_kc = false;       // SLIO_NO_KNN_CERT: every pass searches in full
     bool persist = false;     // SLIO_PERSIST: one persistent launch per update (k_update_persist)
+    bool no_reducer = false;  // SLIO_NO_REDUCER: a fused pass's filter step on its last workgroup to arrive
   } sw;
   // persistent update (k_update_persist): the flag replicas, the CU count and
   // the workgroups the device holds at once (-1: not yet queried)

@@ -1080,9 +1080,9 @@ int slio_state_boxplus(const slio_state* x, const double dx[24], slio_state* out
 int slio_state_boxminus(const slio_state* x1, const slio_state* x2, double dx[24]);
 
 /* ---- diagnostics ----------------------------------------------------------- */
-/* Re-read the SLIO_NO_FUSE / SLIO_NO_FUSE0 / SLIO_PERSIST / SLIO_NO_MFMA /
- * SLIO_EVENT_WAIT / SLIO_NO_KNN_CERT switches of the update path (read once at
- * slio_create). */
+/* Re-read the SLIO_NO_FUSE / SLIO_NO_FUSE0 / SLIO_NO_REDUCER / SLIO_PERSIST /
+ * SLIO_NO_MFMA / SLIO_EVENT_WAIT / SLIO_NO_KNN_CERT switches of the update path
+ * (read once at slio_create). */
 int slio_debug_reload_switches(slio_handle h);
 /* How the last slio_ikf_update_device ran: 1 one persistent launch for all
  * its passes (SLIO_PERSIST=1, single rank, fused configuration, every chunk's
@@ -1105,7 +1105,8 @@ int slio_debug_host_stamps(slio_handle h, int enable, int64_t out[8]);
  * search's 5 nearest and bound, out[1] queries searched in full in passes that write
  * certificates (device-resident passes after the first). */
 int slio_debug_knn_cert(slio_handle h, uint32_t out[2]);
-/* The device-side waits of the next updates on this handle (a persistent
+/* The device-side waits of the next updates on this handle (a fused pass's
+ * reducer workgroup waiting for the launch's segment rows; a persistent
  * update's workgroups waiting for the pass flag; on a group's rank 0, every
  * rank's gate between fused group passes) give up after `ticks` 100 MHz
  * clock ticks instead of 1 s (0 restores 1 s).  A test hook: 1 forces the

@@ -4,7 +4,13 @@ C2 problem, fixed-mode device updates (every pass fused); the stamps of the
 update's last pass: launch start (block 0), then the final workgroup's
 partial issued / segment arrival / row stored / row arrival, the 64 rows
 summed into super rows with the control block staged (one batch over all
-threads), filter step chain, end.  Medians over the updates, microseconds."""
+threads), filter step chain, end.  With a reducer workgroup in the launch
+(the default; SLIO_NO_REDUCER=1 for the tail above) the stamps are the
+reducer's: its start and the control block staged (early in the launch), then
+the last row's partial issued / its segment arrival / the row stored and
+marked ready (by the search workgroup that stored a row last), the mark seen
+by the reducer, that row's sums loaded and the totals formed, filter step
+chain, end.  Medians over the updates, microseconds."""
 import ctypes as C
 import os
 import sys
@@ -30,6 +36,10 @@ st0 = np.concatenate([fr.init_pos, fr.init_rot, [1, 0, 0, 0], synth.AVIA_T_LI, n
 names = [("launch->final's partial", 20, 16), ("segment arrival", 16, 17), ("row sum + store", 17, 18),
          ("row arrival", 18, 19), ("rows + block staged", 19, 4), ("S, w", 4, 9), ("cholesky + solves", 9, 10),
          ("dx + ballot", 10, 11), ("boxplus", 11, 12), ("flags -> P update / end", 12, 8)]
+# reducer path: g_sstamp[44..47] = reducer start, control block staged, last row seen, rows summed
+names_red = [("launch->reducer start", 20, 44), ("control block staged + dx_new", 44, 45),
+             ("launch->last row's partial", 20, 16), ("segment arrival", 16, 17), ("row sum + store + mark", 17, 18),
+             ("mark seen by the reducer", 18, 46), ("row loaded, super rows", 46, 47), ("totals", 47, 4)] + names[5:]
 acc = {m: [] for m in (1, 2, 4)}
 for rep in range(14):
     for maxit in (1, 2, 4):
@@ -40,14 +50,17 @@ for rep in range(14):
         stt = L.SlioIkfStats()
         L.check(lib.slio_ikf_update_device(h, C.byref(xs), L.dptr(P), 0.001, maxit, 0, L.SLIO_MODE_FIXED,
                                            L.ALLREDUCE_FN(), None, C.byref(stt)), "ikf")
-        buf = (C.c_ulonglong * 32)()
+        buf = (C.c_ulonglong * 64)()
         lib.slio_dbg_solve_stamps(buf)
         if rep >= 2:
-            acc[maxit].append(np.array(buf[:32], dtype=np.int64))
+            acc[maxit].append(np.array(buf[:64], dtype=np.int64))
 for maxit in (1, 2, 4):
     d = np.array(acc[maxit])
-    parts = [f"{n}={np.median(d[:, b] - d[:, a]) * 0.01:.2f}" for n, a, b in names]
-    print(f"maxit {maxit} (last pass): " + "  ".join(parts) + f"  total={np.median(d[:, 8] - d[:, 20]) * 0.01:.2f}")
+    red = bool((d[:, 46] != 0).all())
+    parts = [f"{n}={np.median(d[:, b] - d[:, a]) * 0.01:.2f}" for n, a, b in (names_red if red else names)]
+    print(f"maxit {maxit} (last pass{', reducer' if red else ''}): " + "  ".join(parts) +
+          f"  last partial->step end={np.median(d[:, 8] - d[:, 16]) * 0.01:.2f}"
+          f"  total={np.median(d[:, 8] - d[:, 20]) * 0.01:.2f}")
 # fixed mode, maxit 4: per pass k, block 0's start [21 + k + 1 & 3] and the filter step's end
 # [25 + ...]: the pass's span and the boundary to the next pass's start
 d = np.array(acc[4])
