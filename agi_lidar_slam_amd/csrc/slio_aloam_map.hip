@@ -339,7 +339,7 @@ __global__ void k_amap_interleave(const float* __restrict__ x, const float* __re
   out[3 * i + 2] = z[i];
 }
 
-inline int blocks(int64_t n) { return (int)((n + 255) / 256); }
+using lvx::blocks;
 
 std::mutex g_live_mu;
 std::set<void*> g_live;

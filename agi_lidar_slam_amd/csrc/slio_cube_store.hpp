@@ -26,6 +26,10 @@ namespace lvx {
 constexpr uint32_t kDrop = 0xFFFFFFFFu;  // the cube id of a point that leaves the store
 constexpr int kMaxListed = 125;          // the longest cube list gathered at once
 
+// workgroups of 256 threads for n items; 0 for none (grid_blocks of
+// slio_device.hpp launches at least one), so a caller launches only for n > 0
+inline int blocks(int64_t n) { return (int)((n + 255) / 256); }
+
 struct CubeGeom {
   float inv;
   int minb[3];

@@ -1,8 +1,10 @@
-// slio_device.hpp -- what the mapping back-ends (slio_mapopt.hip) use of the
-// IKF core's device runtime (slio_device.hip): the handle's context and map,
-// the error macros and the host entry points that enqueue a search pass, build
-// a map or a scan, or read a few values back.  Internal to the library; both
-// files are HIP translation units.
+// slio_device.hpp -- what the two files of the IKF runtime -- the core with
+// scan preparation (slio_device.hip) and the map (slio_map.hip) -- use of one
+// another, and what the mapping back-ends (slio_mapopt.hip) use of them: the
+// handle's context and map, the error macros, the bounds-check macro of the
+// diagnostic build and the host entry points that enqueue a search pass,
+// build a map or a scan, or read a few values back.  Internal to the library; every file
+// that includes it is a HIP translation unit.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,6 +29,22 @@
       return SLIO_EDEVICE;                                                      \
     }                                                                           \
   } while (0)
+
+#ifdef SLIO_BOUNDS_CHECK
+// diagnostic build only: report and neutralise an out-of-range index
+#define SLIO_BCHK(idx, lim, what)                                                       \
+  do {                                                                                  \
+    if ((int64_t)(idx) < 0 || (int64_t)(idx) >= (int64_t)(lim)) {                       \
+      printf("slio bounds: %s idx %lld lim %lld block %d thread %d\n", what,             \
+             (long long)(idx), (long long)(lim), (int)blockIdx.x, (int)threadIdx.x);     \
+      idx = 0;                                                                          \
+    }                                                                                   \
+  } while (0)
+#else
+#define SLIO_BCHK(idx, lim, what) \
+  do {                            \
+  } while (0)
+#endif
 
 namespace slio {
 
@@ -306,20 +324,48 @@ __device__ __forceinline__ void lego_to_map(const LegoRot& T, float x, float y, 
   oz = -T.sp * x2 + T.cp * z2 + T.tz;
 }
 
+// a rebuilt map gets its block rows once it has been searched this many times
+// unchanged (MapDev::blk_deferred)
+constexpr int kBlkAfterPasses = 8;
+
 struct SolveArgs;  // slio_device.hip
 struct FuseArgs;
 
-// The host entry points, defined in slio_device.hip (not exported from the
-// library).
+// The host entry points the files call across one another (not exported from
+// the library).
 #pragma GCC visibility push(hidden)
-int map_read_sync(Ctx& c);  // MapDev::mu held by the caller
+// ---- slio_device.hip
 PoseDev make_pose(const slio_pose* x);
+hipError_t spin_sync(hipStream_t st);  // polled wait for a stream
 hipError_t readback(hipStream_t st, const Rb* rb, int k);
-int map_refresh(Ctx& c, bool adds_only = false);
 int enqueue_pass(Ctx& c, const PoseDev* Parg, IkfCtl* ctl, int which, int extrinsic_est,
                  const SolveArgs* sa = nullptr, bool with_super = true, bool knn_only = false,
                  const ScanDev* sd = nullptr, const FuseArgs* fuse = nullptr, int persist = 0);
+// the last search pass's ids and distances (k_nbr_derive), before its scan or
+// map changes: MapDev::mu held by the caller / taken shared
+int nbr_settle(Ctx& c);
+int nbr_settle_shared(Ctx& c);
+#ifdef SLIO_BOUNDS_CHECK
+void dbg_set_bounds(int64_t npts, int64_t ncells);  // the limits the search's index checks read
+#endif
+// ---- slio_map.hip
+int map_write_begin(Ctx& c);  // MapDev::mu held exclusively by the caller
+int map_write_end(Ctx& c);
+int map_read_sync(Ctx& c);  // MapDev::mu held by the caller
+void map_attach(Ctx& c, std::shared_ptr<MapDev> m);
+int map_refresh(Ctx& c, bool adds_only = false);
 int grid_blocks(int64_t n);
+int build_blk(MapDev& m, hipStream_t st, const char* who);
+int build_index(MapDev& m, const float4* in, int64_t n, const float mn[3], const float mx[3], hipStream_t st,
+                const char* who, bool with_blk = true, bool in_id_order = false, bool had_points = false);
+// out[i] = {x[i], y[i], z[i], bits(i)}: build_index's input from a SoA cloud (k_pack_ids)
+void pack_ids(const float* x, const float* y, const float* z, int64_t n, float4* out, hipStream_t st);
+// exclusive scan of n flags into rank, enqueued on st (no readback)
+int scan_launch(const uint32_t* flag, uint32_t* rank, int64_t n, hipStream_t st);
+// stable radix sort of n 32-bit (key, value) pairs by the whole key, enqueued on st
+hipError_t sort_pairs32(MapDev::Buf& tmp, const uint32_t* k0, uint32_t* k1, const uint32_t* v0, uint32_t* v1,
+                        int64_t n, hipStream_t st);
+// ---- slio_device.hip: scan preparation
 int ensure_scan_buffers(Ctx& c);
 // downSizeFilterSurf of n device points (dx_, dy_, dz_) into the handle's scan
 int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float* dz_, int64_t n, float leaf,
@@ -328,8 +374,8 @@ int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float* dz_, i
 // concatenation on c's stream, VoxelGrid it with edge `leaf`, and make the
 // result c's map or, as_scan, c's scan.  pass_through (with as_scan only): no
 // VoxelGrid, the concatenation itself becomes the scan, `leaf` is not read.
-// The one map-building entry of the back-ends: the VoxelGrid and the index
-// build stay in slio_device.hip.
+// The one map-building entry of the back-ends: the VoxelGrid is in
+// slio_device.hip, the index build in slio_map.hip.
 int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float leaf, bool as_scan, int64_t counts[2],
                 const char* who, int form = 0, bool pass_through = false);
 #pragma GCC visibility pop

@@ -43,10 +43,12 @@
 
 #include "slio_cube_store.hpp"
 #include "slio_device.hpp"
+#include "slio_fkey.hpp"
 #include "slio_frontend.h"
 #include "slio_livox.hpp"
 #include "slio_lreg.hpp"
 
+using slio::fkey;
 using slio::set_error;
 using slio::MapDev;
 using namespace slio::lvx;
@@ -55,11 +57,6 @@ namespace {
 
 constexpr uint64_t kDropKey = ~0ull;
 constexpr int kSortBits = 45;  // 32 voxel bits + 13 cube bits (kNum < 8191 = the dropped points' field)
-
-__device__ __forceinline__ int32_t fkey(float f) {  // monotone float -> int
-  const int32_t b = __float_as_int(f);
-  return b >= 0 ? b : b ^ 0x7FFFFFFF;
-}
 
 __global__ void k_lvx_append(const float* __restrict__ in, int64_t n, slio::LegoRot T, int cenI, int cenJ, int cenK,
                              float* __restrict__ x, float* __restrict__ y, float* __restrict__ z,
@@ -360,8 +357,6 @@ __global__ void k_lvx_scan_in(const float* __restrict__ in, int64_t n, float* __
   z[i] = c;
   id[i] = (isfinite(a) && isfinite(b) && isfinite(c)) ? 0u : kDrop;
 }
-
-inline int blocks(int64_t n) { return (int)((n + 255) / 256); }
 
 constexpr int64_t kMaxCells = (int64_t)1 << 24;
 

@@ -1,5 +1,5 @@
-// slio_mapopt.hip -- the mapping back-ends on top of the IKF core's device
-// runtime (slio_device.hip, reached through slio_device.hpp): LIO-SAM's
+// slio_mapopt.hip -- the mapping back-ends on top of the IKF runtime
+// (slio_device.hip and slio_map.hip, reached through slio_device.hpp): LIO-SAM's
 // scan-to-map optimisation, its loop-closure ICP pass, its keyframe store and
 // the local-map / loop-cloud assembly, and LeGO-LOAM's mapping (slio_lmap_*).
 // The two mappers share one scan-to-map path: the map-frame scan and its 5-NN

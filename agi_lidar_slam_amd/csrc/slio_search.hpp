@@ -1,5 +1,5 @@
-// slio_search.hpp -- the device search primitives the IKF core
-// (slio_device.hip) and the mapping back-ends (slio_mapopt.hip) both compile:
+// slio_search.hpp -- the device search primitives the IKF runtime
+// (slio_device.hip, slio_map.hip) and the mapping back-ends (slio_mapopt.hip) compile:
 // the grid views a kernel receives, the sorted top-5 list, the exactness bound
 // of a fine cube and the whole-wavefront search on the coarse level.  The
 // library is built without relocatable device code, so every function here is
