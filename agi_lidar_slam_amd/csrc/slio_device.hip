@@ -4470,7 +4470,9 @@ __global__ void k_time_keys(const float* __restrict__ t, int64_t n, uint32_t* __
                             uint32_t* __restrict__ vals) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  keys[i] = (uint32_t)fkey(t[i]) ^ 0x80000000u;  // float order as unsigned
+  // float order as unsigned; t + 0.0f turns -0.0f into +0.0f, so the two
+  // zeros tie as they do under the reference's t[a] < t[b]
+  keys[i] = (uint32_t)fkey(t[i] + 0.0f) ^ 0x80000000u;
   vals[i] = (uint32_t)i;
 }
 
@@ -4490,19 +4492,12 @@ __global__ void k_undistort(const float* __restrict__ x, const float* __restrict
   const float px = x[o], py = y[o], pz = z[o], pt = t[o];
   ot[i] = pt;
   const double tt = (double)pt / double(1000);
-  int lo = -1;
-  if (np >= 2) {
-    int a = 0, b = np - 2;  // largest k in [0, np-2] with offset[k] < tt
-    while (a <= b) {
-      const int m = (a + b) >> 1;
-      if (poses[m].offset_time < tt) {
-        lo = m;
-        a = m + 1;
-      } else {
-        b = m - 1;
-      }
-    }
-  }
+  // largest k in [0, np-2] with offset[k] < tt, by a scan down from the top:
+  // the table has tens of entries and need not increase (an IMU sample
+  // between the previous scan's end and this scan's start has a negative
+  // offset after the leading 0), so no bisection
+  int lo = np - 2;
+  while (lo >= 0 && !(poses[lo].offset_time < tt)) --lo;
   if (lo < 0) {
     ox[i] = px;
     oy[i] = py;
@@ -4512,13 +4507,15 @@ __global__ void k_undistort(const float* __restrict__ x, const float* __restrict
   // The reference's backward loop leaves its point iterator on the first
   // point once that point is done ("if (it_pcl == begin) break"), so every
   // earlier segment whose offset is below that point's time compensates it
-  // again (IMU_Processing.hpp:365-399): mirrored for i == 0.
+  // again (IMU_Processing.hpp:365-399): mirrored for i == 0.  A segment
+  // whose offset is not below the time is passed over, as the reference's
+  // loop condition does per segment; the ones before it are still tried.
   float cx = px, cy = py, cz = pz;
   const int k_end = (i == 0) ? 0 : lo;
   for (int k = lo; k >= k_end; --k) {
     const slio_imu_pose& hd = poses[k];
     const slio_imu_pose& tl = poses[k + 1];
-    if (!(tt > hd.offset_time)) break;
+    if (!(tt > hd.offset_time)) continue;
     const double dt = tt - hd.offset_time;
     const double w[3] = {tl.gyr[0] * dt, tl.gyr[1] * dt, tl.gyr[2] * dt};
     double Ex[9];
@@ -4558,8 +4555,9 @@ __global__ void k_undistort(const float* __restrict__ x, const float* __restrict
 static bool time_keys_sorted(const float* t, int64_t n) {
   uint32_t prev = 0, bad = 0;
   for (int64_t i = 0; i < n; ++i) {
+    const float f = t[i] + 0.0f;  // (-0.0f -> +0.0f, as k_time_keys)
     int32_t b;
-    std::memcpy(&b, t + i, 4);
+    std::memcpy(&b, &f, 4);
     const uint32_t k = (uint32_t)(b >= 0 ? b : b ^ 0x7FFFFFFF) ^ 0x80000000u;
     bad |= (uint32_t)(k < prev);
     prev = k;

@@ -121,7 +121,11 @@ void find_rotation(double pointTime, const double* imuTime, const double* rx, co
 // pcl::VoxelGrid<PointXYZI>::applyFilter with downsample_all_data_ (PCL 1.10
 // VoxelGrid::applyFilter + CentroidPoint) on the points xyzi[pos[q]]; writes
 // the centroids to out, returns their number.  Index ties by position.
-int64_t voxel_grid(const float* xyzi, const std::vector<int64_t>& pos, float leaf, float* out) {
+// pos holds the rows the grid sees (the finite ones); when the voxel index
+// would overflow PCL copies its whole input, non-finite rows included: the
+// rows of *all if given, else pos.
+int64_t voxel_grid(const float* xyzi, const std::vector<int64_t>& pos, float leaf, float* out,
+                   const std::vector<int64_t>* all = nullptr) {
   if (pos.empty()) return 0;
   const float inv = 1.0f / leaf;
   float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
@@ -134,8 +138,8 @@ int64_t voxel_grid(const float* xyzi, const std::vector<int64_t>& pos, float lea
   const int64_t dy = (int64_t)((mx[1] - mn[1]) * inv) + 1;
   const int64_t dz = (int64_t)((mx[2] - mn[2]) * inv) + 1;
   int64_t ns = 0;
-  if (dx * dy * dz > (int64_t)INT32_MAX) {  // PCL: output = input
-    for (int64_t p : pos) std::memcpy(out + (ns++) * 4, xyzi + p * 4, 16);
+  if (dx * dy * dz > (int64_t)INT32_MAX) {  // PCL: output = *input_, every row as it is
+    for (int64_t p : (all ? *all : pos)) std::memcpy(out + (ns++) * 4, xyzi + p * 4, 16);
     return ns;
   }
   int minb[3], divb[3];
@@ -171,7 +175,8 @@ int64_t voxel_grid(const float* xyzi, const std::vector<int64_t>& pos, float lea
 // The same VoxelGrid with PCL 1.10's own index sort: std::sort of
 // {idx, cloud_point_index} with operator< on idx only (voxel_grid.hpp,
 // cloud_point_index_idx), i.e. libstdc++ introsort's order inside a voxel.
-int64_t voxel_grid_pcl_order(const float* xyzi, const std::vector<int64_t>& pos, float leaf, float* out) {
+int64_t voxel_grid_pcl_order(const float* xyzi, const std::vector<int64_t>& pos, float leaf, float* out,
+                             const std::vector<int64_t>* all = nullptr) {
   struct Idx {
     uint32_t idx, cpi;
     bool operator<(const Idx& o) const { return idx < o.idx; }
@@ -189,7 +194,7 @@ int64_t voxel_grid_pcl_order(const float* xyzi, const std::vector<int64_t>& pos,
   const int64_t dz = (int64_t)((mx[2] - mn[2]) * inv) + 1;
   int64_t ns = 0;
   if (dx * dy * dz > (int64_t)INT32_MAX) {
-    for (int64_t p : pos) std::memcpy(out + (ns++) * 4, xyzi + p * 4, 16);
+    for (int64_t p : (all ? *all : pos)) std::memcpy(out + (ns++) * 4, xyzi + p * 4, 16);
     return ns;
   }
   int minb[3], divb[3];
@@ -903,23 +908,25 @@ int orc_lego_features(const orc_lego_params* P, const float* orient, const int32
 
 // downSizeFilterSurf (laserMapping.cpp:683-686, 737-739): pcl::VoxelGrid
 // over a cloud's xyz; non-finite points are skipped (PCL with is_dense
-// false).  pcl_order = 0: ties of the voxel index sort by point index (the
-// device's order); 1: PCL 1.10's std::sort order.  Returns the number of
-// centroids written to ox / oy / oz (capacity n).
+// false), except on the pass-through, which returns all n rows.
+// pcl_order = 0: ties of the voxel index sort by point index (the device's
+// order); 1: PCL 1.10's std::sort order.  Returns the number of centroids
+// written to ox / oy / oz (capacity n).
 extern "C" int64_t orc_voxel_grid_xyz(const float* x, const float* y, const float* z, int64_t n, float leaf,
                                       int pcl_order, float* ox, float* oy, float* oz) {
   std::vector<float> xyzi((size_t)n * 4);
-  std::vector<int64_t> pos;
+  std::vector<int64_t> pos, all((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
+    all[i] = i;
     xyzi[4 * i] = x[i];
     xyzi[4 * i + 1] = y[i];
     xyzi[4 * i + 2] = z[i];
     xyzi[4 * i + 3] = 0.0f;
     if (std::isfinite(x[i]) && std::isfinite(y[i]) && std::isfinite(z[i])) pos.push_back(i);
   }
-  std::vector<float> out(pos.size() * 4 + 4);
-  const int64_t m = pcl_order ? voxel_grid_pcl_order(xyzi.data(), pos, leaf, out.data())
-                              : voxel_grid(xyzi.data(), pos, leaf, out.data());
+  std::vector<float> out((size_t)n * 4 + 4);
+  const int64_t m = pcl_order ? voxel_grid_pcl_order(xyzi.data(), pos, leaf, out.data(), &all)
+                              : voxel_grid(xyzi.data(), pos, leaf, out.data(), &all);
   for (int64_t k = 0; k < m; ++k) {
     ox[k] = out[4 * k];
     oy[k] = out[4 * k + 1];

@@ -7,7 +7,8 @@
 //                        double loop over IMU segments and time-sorted points,
 //                        verbatim in structure: the first point, once reached,
 //                        stays under the pointer and is compensated again by
-//                        every earlier segment whose offset is below its time)
+//                        every earlier segment whose offset is below its time);
+//                        orc_undistort_points runs it alone on a given table
 //   Sophus a621ff SO3::exp (expAndTheta, SMALL_EPS 1e-10, libm sin / cos),
 //   SO3 * vector = Eigen _transformVector, SO3::matrix = toRotationMatrix.
 // The time sort (std::sort with time_list, :266) is taken stable (ties by
@@ -142,6 +143,69 @@ struct Pose {
 
 }  // namespace
 
+// Step 5 (IMU_Processing.hpp:360-401) on its own: the backward double loop
+// over a given IMUpose table (npose x 22: offset, acc, gyr, vel, pos, rot
+// row-major) and the scan-end state, so that crafted tables reach it.  The
+// table need not increase.  Outputs in time order (stable).
+extern "C" int orc_undistort_points(const double* poses22, int npose, const double* state26, const float* x,
+                                    const float* y, const float* z, const float* t, int64_t n, float* ox,
+                                    float* oy, float* oz, float* ot) {
+  St st;
+  std::memcpy(st.s, state26, sizeof st.s);
+  std::vector<Pose> IMUpose(npose > 0 ? npose : 0);
+  for (int k = 0; k < npose; ++k) {
+    const double* o = poses22 + 22 * k;
+    Pose& p = IMUpose[k];
+    p.off = o[0];
+    std::memcpy(p.acc, o + 1, 24);
+    std::memcpy(p.gyr, o + 4, 24);
+    std::memcpy(p.vel, o + 7, 24);
+    std::memcpy(p.pos, o + 10, 24);
+    std::memcpy(p.rot, o + 13, 72);
+  }
+  // backward over the time-sorted points
+  std::vector<int64_t> ord(n);
+  std::iota(ord.begin(), ord.end(), 0);
+  std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return t[a] < t[b]; });
+  for (int64_t i = 0; i < n; ++i) {
+    ox[i] = x[ord[i]];
+    oy[i] = y[ord[i]];
+    oz[i] = z[ord[i]];
+    ot[i] = t[ord[i]];
+  }
+  if (n == 0) return 0;
+  double Re[9], RL[9];
+  matrix(st.rot(), Re);
+  matrix(st.rli(), RL);
+  const double* TL = st.s + 11;
+  int64_t ip = n - 1;
+  for (int kp = (int)IMUpose.size() - 1; kp > 0; --kp) {
+    const Pose& hd = IMUpose[kp - 1];
+    const Pose& tl = IMUpose[kp];
+    for (; ot[ip] / double(1000) > hd.off; --ip) {
+      const double dt = ot[ip] / double(1000) - hd.off;
+      const double w[3] = {tl.gyr[0] * dt, tl.gyr[1] * dt, tl.gyr[2] * dt};
+      double Ex[9], Ri[9];
+      matrix(so3_exp(w), Ex);
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c)
+          Ri[3 * r + c] = (hd.rot[3 * r] * Ex[c] + hd.rot[3 * r + 1] * Ex[3 + c]) + hd.rot[3 * r + 2] * Ex[6 + c];
+      const double Pi[3] = {(double)ox[ip], (double)oy[ip], (double)oz[ip]};
+      double Tei[3], a[3], b[3], cv[3], d[3];
+      for (int k = 0; k < 3; ++k) Tei[k] = ((hd.pos[k] + hd.vel[k] * dt) + ((0.5 * tl.acc[k]) * dt) * dt) - st.s[k];
+      for (int r = 0; r < 3; ++r) a[r] = ((RL[3 * r] * Pi[0] + RL[3 * r + 1] * Pi[1]) + RL[3 * r + 2] * Pi[2]) + TL[r];
+      for (int r = 0; r < 3; ++r) b[r] = ((Ri[3 * r] * a[0] + Ri[3 * r + 1] * a[1]) + Ri[3 * r + 2] * a[2]) + Tei[r];
+      for (int r = 0; r < 3; ++r) cv[r] = ((Re[r] * b[0] + Re[3 + r] * b[1]) + Re[6 + r] * b[2]) - TL[r];
+      for (int r = 0; r < 3; ++r) d[r] = (RL[r] * cv[0] + RL[3 + r] * cv[1]) + RL[6 + r] * cv[2];
+      ox[ip] = (float)d[0];
+      oy[ip] = (float)d[1];
+      oz[ip] = (float)d[2];
+      if (ip == 0) break;
+    }
+  }
+  return 0;
+}
+
 extern "C" int orc_imu_undistort(const double* imu7, int nimu, double pcl_beg, double pcl_end,
                                  double* last_lidar_end, double mean_acc_norm, const double* cov12,
                                  double* acc_s_last, double* angvel_last, double* state26, double* P,
@@ -210,45 +274,5 @@ extern "C" int orc_imu_undistort(const double* imu7, int nimu, double pcl_beg, d
     std::memcpy(o + 10, p.pos, 24);
     std::memcpy(o + 13, p.rot, 72);
   }
-  // step 5: backward over the time-sorted points
-  std::vector<int64_t> ord(n);
-  std::iota(ord.begin(), ord.end(), 0);
-  std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return t[a] < t[b]; });
-  for (int64_t i = 0; i < n; ++i) {
-    ox[i] = x[ord[i]];
-    oy[i] = y[ord[i]];
-    oz[i] = z[ord[i]];
-    ot[i] = t[ord[i]];
-  }
-  if (n == 0) return 0;
-  double Re[9], RL[9];
-  matrix(st.rot(), Re);
-  matrix(st.rli(), RL);
-  const double* TL = st.s + 11;
-  int64_t ip = n - 1;
-  for (int kp = (int)IMUpose.size() - 1; kp > 0; --kp) {
-    const Pose& hd = IMUpose[kp - 1];
-    const Pose& tl = IMUpose[kp];
-    for (; ot[ip] / double(1000) > hd.off; --ip) {
-      const double dt = ot[ip] / double(1000) - hd.off;
-      const double w[3] = {tl.gyr[0] * dt, tl.gyr[1] * dt, tl.gyr[2] * dt};
-      double Ex[9], Ri[9];
-      matrix(so3_exp(w), Ex);
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c)
-          Ri[3 * r + c] = (hd.rot[3 * r] * Ex[c] + hd.rot[3 * r + 1] * Ex[3 + c]) + hd.rot[3 * r + 2] * Ex[6 + c];
-      const double Pi[3] = {(double)ox[ip], (double)oy[ip], (double)oz[ip]};
-      double Tei[3], a[3], b[3], cv[3], d[3];
-      for (int k = 0; k < 3; ++k) Tei[k] = ((hd.pos[k] + hd.vel[k] * dt) + ((0.5 * tl.acc[k]) * dt) * dt) - st.s[k];
-      for (int r = 0; r < 3; ++r) a[r] = ((RL[3 * r] * Pi[0] + RL[3 * r + 1] * Pi[1]) + RL[3 * r + 2] * Pi[2]) + TL[r];
-      for (int r = 0; r < 3; ++r) b[r] = ((Ri[3 * r] * a[0] + Ri[3 * r + 1] * a[1]) + Ri[3 * r + 2] * a[2]) + Tei[r];
-      for (int r = 0; r < 3; ++r) cv[r] = ((Re[r] * b[0] + Re[3 + r] * b[1]) + Re[6 + r] * b[2]) - TL[r];
-      for (int r = 0; r < 3; ++r) d[r] = (RL[r] * cv[0] + RL[3 + r] * cv[1]) + RL[6 + r] * cv[2];
-      ox[ip] = (float)d[0];
-      oy[ip] = (float)d[1];
-      oz[ip] = (float)d[2];
-      if (ip == 0) break;
-    }
-  }
-  return 0;
+  return orc_undistort_points(poses22, *npose, state26, x, y, z, t, n, ox, oy, oz, ot);
 }

@@ -64,6 +64,7 @@ def _bind_map(lib):
     lib.orc_imu_undistort.argtypes = [_DP, C.c_int, C.c_double, C.c_double, _DP, C.c_double, _DP, _DP, _DP,
                                       _DP, _DP, _FP, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP, _FP, _DP,
                                       C.POINTER(C.c_int)]
+    lib.orc_undistort_points.argtypes = [_DP, C.c_int, _DP, _FP, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP, _FP]
     lib.orc_voxel_grid_xyz.restype = C.c_int64
     lib.orc_voxel_grid_xyz.argtypes = [_FP, _FP, _FP, C.c_int64, C.c_float, C.c_int, _FP, _FP, _FP]
     lib.orc_map_new.restype = C.c_void_p
@@ -265,6 +266,25 @@ def imu_undistort(imu: np.ndarray, pcl_beg: float, pcl_end: float, last_lidar_en
             "last_lidar_end_time": lle.value}
 
 
+def undistort_points(poses22: np.ndarray, state26: np.ndarray, pts: np.ndarray, t_ms: np.ndarray):
+    """Step 5 of UndistortPcl alone (IMU_Processing.hpp:360-401): the backward
+    double loop over a given IMUpose table (npose, 22) and the scan-end state.
+    Returns (points (n, 3) in stable time order, their times)."""
+    po = np.ascontiguousarray(poses22, dtype=np.float64).reshape(-1, 22)
+    st = np.ascontiguousarray(state26, dtype=np.float64)
+    p = _f(pts).reshape(-1, 3)
+    n = p.shape[0]
+    x, y, z = (_f(p[:, k]) for k in range(3))
+    t = _f(t_ms)
+    assert t.shape == (n,) and st.shape == (26,)
+    ox, oy, oz, ot = (np.zeros(max(n, 1), np.float32) for _ in range(4))
+    load().orc_undistort_points(po.ctypes.data_as(_DP), po.shape[0], st.ctypes.data_as(_DP),
+                                x.ctypes.data_as(_FP), y.ctypes.data_as(_FP), z.ctypes.data_as(_FP),
+                                t.ctypes.data_as(_FP), n, ox.ctypes.data_as(_FP), oy.ctypes.data_as(_FP),
+                                oz.ctypes.data_as(_FP), ot.ctypes.data_as(_FP))
+    return np.stack([ox[:n], oy[:n], oz[:n]], 1), ot[:n]
+
+
 def s2m_transform(tf, body):
     """pointAssociateToMap at transformTobeMapped (LIO-SAM mapOptmization.cpp:359-373)."""
     t = _f(tf)
@@ -321,7 +341,9 @@ def s2m_normal_equations(tf, clouds):
 
 
 def voxel_grid(pts: np.ndarray, leaf: float, pcl_order: bool = False) -> np.ndarray:
-    """pcl::VoxelGrid centroids of a cloud's xyz (laserMapping downSizeFilterSurf)."""
+    """pcl::VoxelGrid centroids of a cloud's xyz (laserMapping downSizeFilterSurf).
+    Non-finite rows are dropped, except when the voxel index would overflow:
+    then PCL's output is its input, every row as it is."""
     p = _f(pts).reshape(-1, 3)
     x, y, z = (_f(p[:, k]) for k in range(3))
     n = p.shape[0]

@@ -2,10 +2,13 @@
 import numpy as np
 
 
-def make_case(seed=0, first_late=False, n=30000):
+def make_case(seed=0, first_late=False, n=30000, gap=False):
+    """gap: the previous scan ended 4 ms before this one starts and the second
+    IMU sample lies in between, 2 ms before the start: its pose's offset is
+    negative (IMU_Processing.hpp:290, :346-348)."""
     rng = np.random.default_rng(seed)
     beg, end = 100.0, 100.1
-    ts = np.arange(beg - 0.004, end + 0.006, 0.005)
+    ts = np.arange(beg - (0.007 if gap else 0.004), end + 0.006, 0.005)
     w = np.array([0.1, -0.2, 0.8]) + rng.normal(0, 0.01, (ts.size, 3))
     a = np.array([0.3, 0.1, 1.02]) + rng.normal(0, 0.02, (ts.size, 3))
     imu = np.concatenate([ts[:, None], a, w], 1)
@@ -23,6 +26,6 @@ def make_case(seed=0, first_late=False, n=30000):
     state[3:7] /= np.linalg.norm(state[3:7])
     P = np.eye(24) * 1e-3
     cov12 = np.array([0.1] * 3 + [0.1] * 3 + [1e-4] * 3 + [1e-4] * 3)
-    return dict(imu=imu, beg=beg, end=end, last_end=beg - 0.002, mean_acc_norm=float(np.linalg.norm([0.3, 0.1, 1.02])),
+    return dict(imu=imu, beg=beg, end=end, last_end=beg - (0.004 if gap else 0.002), mean_acc_norm=float(np.linalg.norm([0.3, 0.1, 1.02])),
                 cov12=cov12, acc_s_last=np.array([0.1, 0.0, 0.05]), angvel_last=np.array([0.1, -0.2, 0.8]),
                 state=state, P=P, pts=pts, t=t)
