@@ -16,14 +16,15 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libslio.so")
 
-SOURCES = ["slio_device.hip", "slio_map.hip", "slio_mapopt.hip", "slio_ikf.cpp", "slio_imu.cpp", "slio_s2m.cpp",
-           "slio_lio.hip", "slio_lego_odom.hip", "slio_lmap.cpp", "slio_livox.hip", "slio_livox.cpp", "slio_lreg.hip",
-           "slio_lreg.cpp", "slio_aloam.hip", "slio_aloam.cpp", "slio_aloam_odom.hip", "slio_aloam_odom.cpp",
-           "slio_aloam_map.hip", "slio_aloam_map.cpp", "slio_llreg.hip", "slio_llreg.cpp"]
+SOURCES = ["slio_device.hip", "slio_map.hip", "slio_scan.hip", "slio_mapopt.hip", "slio_ikf.cpp", "slio_imu.cpp",
+           "slio_s2m.cpp", "slio_lio.hip", "slio_lego_odom.hip", "slio_lmap.cpp", "slio_cube_store.hip",
+           "slio_livox.hip", "slio_livox.cpp", "slio_lreg.hip", "slio_lreg.cpp", "slio_aloam.hip", "slio_aloam.cpp",
+           "slio_aloam_odom.hip", "slio_aloam_odom.cpp", "slio_aloam_map.hip", "slio_aloam_map.cpp", "slio_llreg.hip",
+           "slio_llreg.cpp"]
 HEADERS = ["slio_common.hpp", "slio_plane.hpp", "slio_so3.hpp", "slio_cvsolve.hpp", "slio_lego_odom.hpp",
            "slio_device.hpp", "slio_search.hpp", "slio_livox.hpp", "slio_lreg.hpp", "slio_icp.hpp",
            "slio_aloam.hpp", "slio_aloam_odom.hpp", "slio_aloam_map.hpp", "slio_cube_store.hpp",
-           "slio_llreg.hpp", "slio_fkey.hpp"]
+           "slio_llreg.hpp", "slio_fkey.hpp", "slio_voxel.hpp"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [

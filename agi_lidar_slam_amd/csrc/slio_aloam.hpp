@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "slio_common.hpp"
+#include "slio_voxel.hpp"
 
 namespace slio {
 namespace aloam {
@@ -147,6 +148,7 @@ SLIO_HD inline void sector(int start, int end, int j, int* sp, int* ep) {
 
 // pcl::VoxelGrid<PointXYZI>::applyFilter's grid from the list's bounding box
 // (the restatement the LeGO front-end's per-ring filter uses, slio_lio.hip)
+// Kept apart from voxel_geometry (slio_voxel.hpp): float min / max in, no guard for a span that is not finite.
 struct Grid {
   float inv;
   int minb[3], mul[3];
@@ -170,10 +172,7 @@ SLIO_HD inline Grid make_grid(const float mn[3], const float mx[3], float leaf) 
   return g;
 }
 SLIO_HD inline uint32_t voxel_of(const Grid& g, float x, float y, float z) {
-  const int i0 = (int)(floorf(x * g.inv) - (float)g.minb[0]);
-  const int i1 = (int)(floorf(y * g.inv) - (float)g.minb[1]);
-  const int i2 = (int)(floorf(z * g.inv) - (float)g.minb[2]);
-  return (uint32_t)(i0 * g.mul[0] + i1 * g.mul[1] + i2 * g.mul[2]);
+  return voxel_index(x, y, z, g.inv, g.minb, g.mul);
 }
 
 }  // namespace aloam

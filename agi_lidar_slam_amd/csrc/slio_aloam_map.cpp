@@ -1,7 +1,7 @@
 // slio_aloam_map.cpp -- A-LOAM's laserMapping on the host, callable without a
 // GPU (src/A-LOAM/src/laserMapping.cpp :326-893): the cube array as one vector
 // per cube, the 5-NN as a brute-force scan of the valid cubes, the VoxelGrid
-// as the cube store states it (slio_livox.hip), and the fits, the factors, the
+// as the cube store states it (slio_cube_store.hip), and the fits, the factors, the
 // sums and the Levenberg-Marquardt over the formulas of slio_aloam_map.hpp,
 // which the kernels of slio_aloam_map.hip share.  It is what checks the
 // device's parallel restatement where there is no GPU.
@@ -13,6 +13,7 @@
 #include "slio_aloam_map.hpp"
 #include "slio_frontend.h"
 #include "slio_livox.hpp"
+#include "slio_voxel.hpp"
 
 using slio::set_error;
 using namespace slio::amap;
@@ -28,10 +29,11 @@ bool finite_pose(const double* q, const double* t) {
   return true;
 }
 
-// The cube store's VoxelGrid of one cloud (n x 3): k_lvx_geom's geometry,
-// k_lvx_keys' voxel index, a stable sort, k_lvx_centroids' float sums in the
-// sorted order; a leaf too small for the cloud passes it through.  Points that
-// are not finite are dropped first.
+// The cube store's VoxelGrid of one cloud (n x 3): k_lvx_box's box in key
+// order, the geometry and the voxel index k_lvx_geom and k_lvx_keys call
+// (slio_voxel.hpp), a stable sort, k_lvx_centroids' float sums in the sorted
+// order; a leaf too small for the cloud passes it through.  Points that are
+// not finite are dropped first.
 void voxel_grid(const std::vector<float>& in, float leaf, std::vector<float>& out) {
   std::vector<float> p;
   for (size_t i = 0; i + 2 < in.size(); i += 3)
@@ -39,40 +41,26 @@ void voxel_grid(const std::vector<float>& in, float leaf, std::vector<float>& ou
       p.insert(p.end(), in.begin() + i, in.begin() + i + 3);
   const size_t n = p.size() / 3;
   out.clear();
-  if (!n) return;
-  float mn[3], mx[3];
-  for (int a = 0; a < 3; ++a) mn[a] = mx[a] = p[a];
-  for (size_t i = 1; i < n; ++i)
+  // (the count, box[6], is only tested against 0)
+  int32_t box[7] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, n ? 1 : 0};
+  for (size_t i = 0; i < n; ++i)
     for (int a = 0; a < 3; ++a) {
-      mn[a] = std::min(mn[a], p[3 * i + a]);
-      mx[a] = std::max(mx[a], p[3 * i + a]);
+      int32_t k;  // (fkey of slio_fkey.hpp, which is HIP only)
+      std::memcpy(&k, &p[3 * i + a], 4);
+      k = k >= 0 ? k : k ^ 0x7FFFFFFF;
+      box[a] = std::min(box[a], k);
+      box[3 + a] = std::max(box[3 + a], k);
     }
-  const float inv = 1.0f / leaf;
-  int64_t dd[3];
-  for (int a = 0; a < 3; ++a) {
-    const float span = (mx[a] - mn[a]) * inv;
-    dd[a] = std::isfinite(span) && span < 9.2e18f ? (int64_t)span + 1 : INT64_MAX / 4;
-  }
-  bool pass = dd[0] > INT32_MAX || dd[1] > INT32_MAX || dd[2] > INT32_MAX;
-  if (!pass) {
-    const int64_t d01 = dd[0] * dd[1];
-    pass = d01 > INT32_MAX || d01 * dd[2] > (int64_t)INT32_MAX;
-  }
-  if (pass) {
+  slio::VoxelGeom g;
+  const slio::VoxelKind kind = slio::voxel_geometry(box, leaf, &g);
+  if (kind == slio::kVoxelNone) return;
+  if (kind == slio::kVoxelPass) {
     out = p;
     return;
   }
-  int minb[3], div[3];
-  for (int a = 0; a < 3; ++a) {
-    minb[a] = (int)floorf(mn[a] * inv);
-    div[a] = (int)floorf(mx[a] * inv) - minb[a] + 1;
-  }
-  const int mul[3] = {1, div[0], div[0] * div[1]};
   std::vector<std::pair<uint32_t, uint32_t>> key(n);
   for (size_t i = 0; i < n; ++i) {
-    uint32_t v = 0;
-    for (int a = 0; a < 3; ++a) v += (uint32_t)((int)(floorf(p[3 * i + a] * inv) - (float)minb[a]) * mul[a]);
-    key[i] = {v, (uint32_t)i};
+    key[i] = {slio::voxel_index(p[3 * i], p[3 * i + 1], p[3 * i + 2], g.inv, g.minb, g.mul), (uint32_t)i};
   }
   std::stable_sort(key.begin(), key.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
   for (size_t i = 0; i < n;) {

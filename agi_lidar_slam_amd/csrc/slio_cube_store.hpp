@@ -1,10 +1,10 @@
-// slio_cube_store.hpp -- the rolling cube store of slio_livox.hip, reachable
-// from the other translation unit that keeps a LOAM cube map on the device
-// (slio_aloam_map.hip).  Internal to the library; HIP only.
+// slio_cube_store.hpp -- the rolling cube store (slio_cube_store.hip) of the
+// two translation units that keep a LOAM cube map on the device
+// (slio_livox.hip, slio_aloam_map.hip).  Internal to the library; HIP only.
 //
 // Per class the store is ONE SoA of points sorted by cube index with a
 // 4852-entry offset table; every change is one pass over the whole class and
-// one host wait (the header comment of slio_livox.hip says how).  The array's
+// one host wait (the header comment of slio_cube_store.hip says how).  The array's
 // three extents are members: livox_mapping's is 21 x 11 x 21, A-LOAM's
 // 21 x 21 x 11, both kNum = 4851 cubes, index i + W j + W H k.  A mapper brings
 // its own append kernel (its pose arithmetic and its cube index) and its own

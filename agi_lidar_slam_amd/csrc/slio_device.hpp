@@ -1,6 +1,7 @@
-// slio_device.hpp -- what the two files of the IKF runtime -- the core with
-// scan preparation (slio_device.hip) and the map (slio_map.hip) -- use of one
-// another, and what the mapping back-ends (slio_mapopt.hip) use of them: the
+// slio_device.hpp -- what the three files of the IKF runtime -- the core
+// (slio_device.hip), the map (slio_map.hip) and scan preparation
+// (slio_scan.hip) -- use of one another, and what the mapping back-ends
+// (slio_mapopt.hip) and the cube store (slio_cube_store.hip) use of them: the
 // handle's context and map, the error macros, the bounds-check macro of the
 // diagnostic build and the host entry points that enqueue a search pass,
 // build a map or a scan, or read a few values back.  Internal to the library; every file
@@ -345,6 +346,7 @@ int enqueue_pass(Ctx& c, const PoseDev* Parg, IkfCtl* ctl, int which, int extrin
 // map changes: MapDev::mu held by the caller / taken shared
 int nbr_settle(Ctx& c);
 int nbr_settle_shared(Ctx& c);
+int ensure_scan_buffers(Ctx& c);  // the scan and the pass's per-point outputs, allocated once
 #ifdef SLIO_BOUNDS_CHECK
 void dbg_set_bounds(int64_t npts, int64_t ncells);  // the limits the search's index checks read
 #endif
@@ -365,8 +367,7 @@ int scan_launch(const uint32_t* flag, uint32_t* rank, int64_t n, hipStream_t st)
 // stable radix sort of n 32-bit (key, value) pairs by the whole key, enqueued on st
 hipError_t sort_pairs32(MapDev::Buf& tmp, const uint32_t* k0, uint32_t* k1, const uint32_t* v0, uint32_t* v1,
                         int64_t n, hipStream_t st);
-// ---- slio_device.hip: scan preparation
-int ensure_scan_buffers(Ctx& c);
+// ---- slio_scan.hip
 // downSizeFilterSurf of n device points (dx_, dy_, dz_) into the handle's scan
 int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float* dz_, int64_t n, float leaf,
                  int64_t* n_down);
@@ -375,7 +376,7 @@ int voxel_device(Ctx& c, const float* dx_, const float* dy_, const float* dz_, i
 // result c's map or, as_scan, c's scan.  pass_through (with as_scan only): no
 // VoxelGrid, the concatenation itself becomes the scan, `leaf` is not read.
 // The one map-building entry of the back-ends: the VoxelGrid is in
-// slio_device.hip, the index build in slio_map.hip.
+// slio_scan.hip, the index build in slio_map.hip.
 int kf_assemble(Ctx& c, const std::vector<KfSeg>& seg, int64_t n, float leaf, bool as_scan, int64_t counts[2],
                 const char* who, int form = 0, bool pass_through = false);
 #pragma GCC visibility pop

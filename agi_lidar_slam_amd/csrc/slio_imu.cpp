@@ -4,7 +4,7 @@
 // (include/esekfom.hpp:82-95; get_f / df_dx / df_dw of use-ikfom.hpp:45-124),
 // which is a short sequential 24-D recursion, and the IMUpose table
 // (Pose6D, common_lib.h) it produces.  The per-point back-propagation over
-// that table runs on the device (slio_device.hip, k_undistort).
+// that table runs on the device (slio_scan.hip, k_undistort).
 #include <cmath>
 #include <cstring>
 

@@ -43,7 +43,7 @@ namespace slio {
 namespace lvx {
 
 #if defined(__HIPCC__)
-// The search grid over a gathered map (slio_livox.hip builds it, k_lvx_pass in
+// The search grid over a gathered map (slio_cube_store.hip builds it, k_lvx_pass in
 // slio_mapopt.hip reads it): cells of edge h, x fastest, cell of a coordinate
 // v = floorf((v - o) * inv_h), the map's points in cells 1 .. n - 3 of every
 // axis at least (two cells of padding below, two above), pts sorted by cell

@@ -12,8 +12,8 @@
 //   * sharing one map among handles (map_write_begin / _end, map_read_sync,
 //     map_attach) and the slio_map_* C ABI.
 //
-// What this file, slio_device.hip and the mapping back-ends use of one another
-// is declared in slio_device.hpp.
+// What this file, slio_device.hip, slio_scan.hip and the mapping back-ends use
+// of one another is declared in slio_device.hpp.
 // Built like slio_device.hip, with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>

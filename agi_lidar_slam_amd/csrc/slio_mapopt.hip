@@ -1,6 +1,6 @@
 // slio_mapopt.hip -- the mapping back-ends on top of the IKF runtime
-// (slio_device.hip and slio_map.hip, reached through slio_device.hpp): LIO-SAM's
-// scan-to-map optimisation, its loop-closure ICP pass, its keyframe store and
+// (slio_device.hip, slio_map.hip and slio_scan.hip, reached through
+// slio_device.hpp): LIO-SAM's scan-to-map optimisation, its loop-closure ICP pass, its keyframe store and
 // the local-map / loop-cloud assembly, and LeGO-LOAM's mapping (slio_lmap_*).
 // The two mappers share one scan-to-map path: the map-frame scan and its 5-NN
 // (s2m_search), the per-point coefficient (s2m_point_coeff), the LM row

@@ -448,6 +448,43 @@ def test_loop_cloud_assembly(L, oracle_mod):
         s2m.close()
 
 
+def test_loop_cloud_as_scan_without_a_point(L):
+    """The as_scan assembly with an empty segment table: key 0's clouds are
+    empty (SIZES[0] == 0), so nothing is gathered and the destination's scan
+    becomes empty, as it does for no key at all; an assembly afterwards gives
+    what it gave before."""
+    from agi_lidar_slam_amd.lio_sam import ScanToMap
+    corner, surf = draw_keyframes(20261020), draw_keyframes(20261021)
+    poses_all = np.stack([key_pose(k) for k in range(len(SIZES))])
+    lib = L.load()
+    s2m = ScanToMap(max_points=4000)
+    hl = s2m.loop_handle()
+
+    def as_scan(keys):
+        key = np.asarray(keys, np.int32)
+        pose = np.ascontiguousarray(poses_all[key].reshape(-1, 6), np.float32)
+        cnt = np.full(2, -1, np.int64)
+        L.check(lib.slio_s2m_loop_cloud(hl, s2m.hc, s2m.hs, L.iptr(key) if len(keys) else None,
+                                        L.fptr(pose) if len(keys) else None, len(keys), 0.4, 1, L.i64ptr(cnt)),
+                "loop_cloud")
+        b, e = C.c_int64(-1), C.c_int64(-1)
+        L.check(lib.slio_shard_range(hl, C.byref(b), C.byref(e)), "shard_range")  # (one rank: the whole scan)
+        assert (b.value, e.value) == (0, cnt[1])
+        return cnt.tolist(), scan_download(L, hl, int(cnt[1]))
+
+    try:
+        for i in range(len(SIZES)):
+            assert s2m.push_keyframe(corner[i], surf[i]) == i
+        cnt4, scan4 = as_scan([4])
+        assert cnt4[0] == 2 * SIZES[4] and 0 < cnt4[1] <= cnt4[0]
+        for keys in ([0], [0, 0], []):
+            assert as_scan(keys)[0] == [0, 0]
+        cnt, scan = as_scan([4])
+        assert cnt == cnt4 and scan.tobytes() == scan4.tobytes()
+    finally:
+        s2m.close()
+
+
 # ---- perform_loop_closure -------------------------------------------------------
 def loop_case(points_per_key, dt=4.0):
     """Twelve keyframes cut from the scene (each its own draw of the same
